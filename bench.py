@@ -2,8 +2,18 @@
 """Headline benchmark: device-resident Shamir 3-of-5 split + reconstruct over
 GF(2^521 - 1) of one 2^24-element int64 vector (BASELINE.json `metric`, configs 2+3).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does only what the headline figure needs: it sets the inputs up,
+warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given and prints the line.  Everything else the line can
+carry is measured or checked only with --full: `parity`, the same-buffer
+ceilings and `roofline.placement`, `weak_scaling`, `config4`, `config5`, `rows`
+and `cpu_baseline` (each still switched by its own option, as before).
+--dump-outputs DIR writes a fixed, seeded sample of what the last timed step
+computed (`shares.npy`, `reconstructed.npy`, `sample_elements.npy`: see
+dump_outputs); the inputs are seeded, so two builds can be compared file by file.
 
 `python bench.py --gpus N` with N > 1 and no launcher environment starts
 `torch.distributed.run` with N ranks as a child process and relays rank 0's
@@ -17,12 +27,12 @@ over --placements separately allocated share buffers, and the line reports
 the split's rate per buffer (`roofline.placement`).  Strong scaling, as
 the metric names it: ONE 2^24-element vector, rank r splitting its tile-aligned
 shard (dist.shard_range); value = 2^24 / max-over-ranks time per step.  At
-N > 1 the line also carries `weak_scaling` (2^24 elements per GPU).
+N > 1 the --full line also carries `weak_scaling` (2^24 elements per GPU).
 
 Prints ONE JSON line (rank 0) with `roofline` for the dominant kernel (split;
 its average launch time from HIP events on the launch stream, algorithmic
-bytes 470 B/element) and `cpu_baseline` (the pure-Python restatement of the
-reference, oracle/py_shamir.py, 1 core, a time-bounded sample).
+bytes 470 B/element) and, with --full, `cpu_baseline` (the pure-Python
+restatement of the reference, oracle/py_shamir.py, 1 core, a time-bounded sample).
 """
 from __future__ import annotations
 
@@ -1138,6 +1148,40 @@ def load_traffic(path: str):
         return None
 
 
+DUMP_TILES = 256  # tiles of 256 elements sampled by --dump-outputs (46 MB of .npy at n = 5)
+
+
+def dump_outputs(path: str, shares, rec, N: int, suffix: str = "") -> None:
+    """What the last timed step computed, as a caller of the path receives it:
+    the share block (split) and the int64 vector (reconstruct), on a fixed
+    sample of elements -- the first and last tile and a seeded choice of the
+    others, DUMP_TILES tiles in all (every element where N is smaller).
+    float64 holds every value exactly:
+      shares.npy             [n, m, 17]  share x = 1..n of sampled element j as 17 little-endian 32-bit limbs
+      reconstructed.npy      [m, 2]      low and high 32-bit word of the int64 result
+      sample_elements.npy    [m]         the elements' indices in the rank's vector"""
+    from delta_node.crypto.shamir import field
+
+    ntiles = (N + field.TILE - 1) // field.TILE
+    if ntiles > DUMP_TILES:
+        inner = np.random.default_rng(2024).choice(ntiles - 2, DUMP_TILES - 2, replace=False) + 1
+        tiles = np.sort(np.concatenate([[0], inner, [ntiles - 1]])).astype(np.int64)
+    else:
+        tiles = np.arange(ntiles, dtype=np.int64)
+    elems = (tiles[:, None] * field.TILE + np.arange(field.TILE)).reshape(-1)
+    valid = elems < N
+    elems = elems[valid]
+    tsel = torch.from_numpy(tiles).to(shares.device)
+    esel = torch.from_numpy(elems).to(rec.device)
+    rows = shares.view(shares.shape[0], ntiles, field.TILE_BYTES)[:, tsel].cpu().numpy()
+    limbs = np.stack([field.vec_to_limbs(r.reshape(-1), len(tiles) * field.TILE)[valid] for r in rows])
+    words = rec[esel].cpu().numpy().view(np.uint32).reshape(-1, 2)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, f"shares{suffix}.npy"), limbs.astype(np.float64))
+    np.save(os.path.join(path, f"reconstructed{suffix}.npy"), words.astype(np.float64))
+    np.save(os.path.join(path, f"sample_elements{suffix}.npy"), elems.astype(np.float64))
+
+
 def free_port() -> int:
     import socket
 
@@ -1195,6 +1239,13 @@ def main():
                          "depends on the physical pages of its share buffer, DESIGN.md §5.1)")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also check the timed outputs (parity) and measure everything beside the headline: the "
+                         "same-buffer ceilings and placements, weak scaling, configs 4 and 5, the rows and the CPU "
+                         "baselines (each as its own option below says); without it those options do nothing")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write a fixed sample of the last step's share block and "
+                         "reconstructed vector to DIR/<name>.npy (float64, exact; see dump_outputs)")
     ap.add_argument("--log2n", type=int, default=24, help="elements of the vector = 2^log2n (sharded over the ranks)")
     ap.add_argument("--t", type=int, default=3)
     ap.add_argument("--shares", type=int, default=5)
@@ -1215,6 +1266,9 @@ def main():
     ap.add_argument("--cold", type=int, default=1, help="also time the first make_shares_vec / config-5 round "
                                                          "of fresh processes (with --rows; N=1 only)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline only
+        args.rows = args.config4 = args.config5 = args.cold = 0
+        args.cpu_budget = 0.0
 
     if "WORLD_SIZE" not in os.environ:
         if (args.gpus or 1) > 1:
@@ -1341,33 +1395,38 @@ def main():
     last = (args.steps - 1) % nbuf if args.steps else 0
     shares = share_bufs[last]
     share_rows = row_sets[last]
-    roundtrip = bool(torch.equal(rec, sec))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, shares, rec, N, f".rank{rank}" if world > 1 else "")
+    roundtrip = oracle_ok = ref_digest_ok = None
     sample = min(2048, N)
-    from oracle import c_oracle
+    all_ok = True
+    if args.full:
+        roundtrip = bool(torch.equal(rec, sec))
+        from oracle import c_oracle
 
-    co_h = np.stack([field.vec_to_limbs(coeffs[j, : field.vec_bytes(sample)].cpu().numpy(), sample)
-                     for j in range(t - 1)], axis=1)
-    want = c_oracle.split(sec_h[:sample], co_h, t, n)
-    got = np.stack([field.vec_to_limbs(shares[x, : field.vec_bytes(sample)].cpu().numpy(), sample) for x in range(n)])
-    oracle_ok = bool(np.array_equal(got, want))
-    bufs_equal = all(bool(torch.equal(sb, shares)) for sb in share_bufs)
-    # the headline workload IS the reference's split_t3n5_2e24 digest case
-    # (secrets_int64(1, 2^24), random.seed(1)): the timed share block's digest
-    # against the one the reference itself produced (tests/golden/manifest.json)
-    ref_digest_ok = None
-    if world == 1 and N_total == (1 << 24) and (t, n) == (3, 5):
-        ref_digest_ok = reference_digest_equal(shares, N, "split_t3n5_2e24")
-    all_ok = roundtrip and oracle_ok and bufs_equal and ref_digest_ok is not False
-    if dist_on:  # every rank's parity, not only rank 0's
-        fl = torch.tensor([int(all_ok)], dtype=torch.int32, device=cdev)
-        torch.distributed.all_reduce(fl, op=torch.distributed.ReduceOp.MIN)
-        all_ok = bool(fl.item())
+        co_h = np.stack([field.vec_to_limbs(coeffs[j, : field.vec_bytes(sample)].cpu().numpy(), sample)
+                         for j in range(t - 1)], axis=1)
+        want = c_oracle.split(sec_h[:sample], co_h, t, n)
+        got = np.stack([field.vec_to_limbs(shares[x, : field.vec_bytes(sample)].cpu().numpy(), sample)
+                        for x in range(n)])
+        oracle_ok = bool(np.array_equal(got, want))
+        bufs_equal = all(bool(torch.equal(sb, shares)) for sb in share_bufs)
+        # the headline workload IS the reference's split_t3n5_2e24 digest case
+        # (secrets_int64(1, 2^24), random.seed(1)): the timed share block's digest
+        # against the one the reference itself produced (tests/golden/manifest.json)
+        if world == 1 and N_total == (1 << 24) and (t, n) == (3, 5):
+            ref_digest_ok = reference_digest_equal(shares, N, "split_t3n5_2e24")
+        all_ok = roundtrip and oracle_ok and bufs_equal and ref_digest_ok is not False
+        if dist_on:  # every rank's parity, not only rank 0's
+            fl = torch.tensor([int(all_ok)], dtype=torch.int32, device=cdev)
+            torch.distributed.all_reduce(fl, op=torch.distributed.ReduceOp.MIN)
+            all_ok = bool(fl.item())
 
     # ---- same-buffer ceilings: the split's bytes through the same pages ----
     split_bytes = N * (8 + (t - 1) * FE_BYTES + n * FE_BYTES)
     placement = None
     ceiling = recon_ceiling = None
-    if N >= (1 << 20):
+    if args.full and N >= (1 << 20):
         fr = [split_bytes / (ms * 1e-3) / 1e9 / PEAK_HBM_GBPS for ms in split_by_buf]
         # the same split into blocks a caller allocates (before the ceiling
         # probes, which overwrite the timed blocks: the equality check needs them)
@@ -1391,7 +1450,7 @@ def main():
 
     # ---- N > 1: the weak-scaling figure (2^log2n elements per GPU) --------
     weak = None
-    if world > 1:
+    if args.full and world > 1:
         del shares, coeffs, share_rows, rec, sec
         torch.cuda.empty_cache()
         ssw = shamir.SecretShare(t)
@@ -1485,7 +1544,7 @@ def main():
                         **recon_ceiling, "GBps": recon_bytes / (recon_ceiling["ms"] * 1e-3) / 1e9,
                         "reconstruct_frac_of_ceiling": recon_ceiling["ms"] / recon_ms}},
         "parity": {"roundtrip_equal": roundtrip, "c_oracle_sample_equal": oracle_ok, "sample": sample,
-                   "reference_digest_equal": ref_digest_ok, "all_ranks_ok": all_ok},
+                   "reference_digest_equal": ref_digest_ok, "all_ranks_ok": all_ok if args.full else None},
         # share blocks memory.share_block mapped, write-probed and freed to place
         # this run's timed blocks (their fractions: roofline.placement; the same
         # split on caller-allocated blocks: roofline.placement.caller_blocks)

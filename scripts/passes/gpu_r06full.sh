@@ -20,10 +20,10 @@ tail -2 $O/pytest_gpu.log
 echo "== msv overhead" && timeout -k 10 200 python scripts/msv_overhead.py > $O/msv_overhead.json 2>&1 || rc=$?
 cut -c1-600 $O/msv_overhead.json
 [ $rc -ne 0 ] && { echo "== rc $rc"; exit $rc; }
-echo "== bench" && timeout -k 10 700 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err || rc=$?
+echo "== bench" && timeout -k 10 700 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err || rc=$?
 cut -c1-300 $O/bench_n1.json
 [ $rc -ne 0 ] && { echo "== rc $rc"; tail -5 $O/bench_n1.err; exit $rc; }
-echo "== rocprof" && cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_full -o run --output-format csv -- python3 "$R/bench.py" --cpu-budget 0 --cold 0 > "$R/$O/bench_under_rocprof.json" 2> "$R/$O/rocprof.err" || rc=$?
+echo "== rocprof" && cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_full -o run --output-format csv -- python3 "$R/bench.py" --full --cpu-budget 0 --cold 0 > "$R/$O/bench_under_rocprof.json" 2> "$R/$O/rocprof.err" || rc=$?
 cd "$R" && mkdir -p $O/prof && find /tmp/prof_full -name "*stats.csv" -exec cp {} $O/prof/ \;
 [ $rc -ne 0 ] && { echo "== rc $rc"; tail -5 $O/rocprof.err; exit $rc; }
 grep -E "split_kernel|reconstruct_kernel|mt_gen_pc|mt_jump" $O/prof/*kernel_stats.csv | cut -c1-200 | head -8

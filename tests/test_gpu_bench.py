@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_gpus_2_launches_two_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["DN_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log2n", "20",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--log2n", "20",
                         "--rows", "0", "--config4", "0", "--config5", "0", "--cpu-budget", "0",
                         "--steps", "4", "--warmup", "1", "--placements", "2"],
                        capture_output=True, text=True, env=env, timeout=110)
@@ -45,8 +45,9 @@ def test_bench_under_launcher_world1_rccl():
         port = so.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr=127.0.0.1", f"--master-port={port}", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--log2n", "20", "--rows", "0", "--config4", "1", "--config4-log2n", "20",
-                        "--config5", "0", "--cpu-budget", "0", "--steps", "2", "--warmup", "1", "--placements", "2"],
+                        "--full", "--gpus", "1", "--log2n", "20", "--rows", "0", "--config4", "1",
+                        "--config4-log2n", "20", "--config5", "0", "--cpu-budget", "0", "--steps", "2",
+                        "--warmup", "1", "--placements", "2"],
                        capture_output=True, text=True, env=env, timeout=110)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -60,7 +61,7 @@ def test_bench_rows_small():
     code runs (a row that raises fails the driver's bench line) and its parity
     flags hold."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log2n", "18", "--steps", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--log2n", "18", "--steps", "2",
                         "--warmup", "1", "--placements", "2", "--config4", "0", "--config5", "0",
                         "--cpu-budget", "0"],
                        capture_output=True, text=True, env=env, timeout=110)
@@ -76,6 +77,47 @@ def test_bench_rows_small():
     assert rows["draw_split"]["equal_draw_then_split_and_state"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries the
+    headline only; --dump-outputs writes the last step's share block and
+    reconstructed vector on its fixed sample (2^18 elements = 1024 tiles, so
+    the seeded choice of 256 tiles runs), float64 and exact: the reconstructed
+    words are the seeded secrets', and tile 0's shares are the C oracle's split
+    of them with the coefficients random.Random(1) yields."""
+    import numpy as np
+
+    from oracle import c_oracle
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--log2n", "18",
+                        "--steps", "3", "--warmup", "1", "--placements", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=env, timeout=110)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx((1 << 18) / (line["ms_per_step"] * 1e-3), rel=1e-9)
+    assert line["unit"] == "elements/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    for k in ("rows", "config4", "config5", "cpu_baseline", "weak_scaling"):
+        assert k not in line, k
+    assert line["roofline"]["placement"] is None and line["parity"]["all_ranks_ok"] is None
+    assert sorted(p.name for p in out.iterdir()) == ["reconstructed.npy", "sample_elements.npy", "shares.npy"]
+    elems, rec, sh = (np.load(out / f"{k}.npy") for k in ("sample_elements", "reconstructed", "shares"))
+    assert elems.dtype == rec.dtype == sh.dtype == np.float64
+    m = 256 * 256
+    assert elems.shape == (m,) and rec.shape == (m, 2) and sh.shape == (5, m, 17)
+    assert sum(a.nbytes for a in (elems, rec, sh)) <= 64e6
+    idx = elems.astype(np.int64)
+    assert idx[0] == 0 and idx[-1] == (1 << 18) - 1 and np.all(np.diff(idx) > 0)
+    sec = np.random.default_rng(1).integers(-(1 << 63), (1 << 63) - 1, size=1 << 18, endpoint=True, dtype=np.int64)
+    got = (rec[:, 0].astype(np.uint64) | (rec[:, 1].astype(np.uint64) << np.uint64(32))).view(np.int64)
+    assert np.array_equal(got, sec[idx])
+    want = c_oracle.split(sec[:256], c_oracle.draw_coeffs(1, 256, 2), 3, 5)
+    assert np.array_equal(sh[:, :256].astype(np.uint32), want)
+
+
 @pytest.mark.timeout(400)
 def test_bench_gpus_8_driver_command_rehearsal():
     """The driver's N=8 command, rehearsed with 8 gloo ranks on the box's one
@@ -84,7 +126,7 @@ def test_bench_gpus_8_driver_command_rehearsal():
     timed in the same run (cpu_baseline at every world size)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["DN_DIST_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--log2n", "20",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--log2n", "20",
                         "--config4", "1", "--config4-log2n", "20", "--rows", "0", "--config5", "0",
                         "--cpu-budget", "2", "--steps", "4", "--warmup", "1", "--placements", "2"],
                        capture_output=True, text=True, env=env, timeout=380)
