@@ -194,6 +194,36 @@ __device__ __forceinline__ void store_reduced(rsrc_t r, uint32_t w, uint32_t D[k
   }
 }
 
+// The same two stores with the lane's byte offsets given (o4 in a 32-bit limb
+// plane, o2 in the 16-bit top plane) instead of an element index of the
+// descriptor's first tile: a descriptor that spans two tiles (mt19937_device.hip,
+// emit_pieces).  Copies, not a common core under store_fe_b / store_reduced:
+// routing those two through an offset-taking form changed the register
+// allocation and schedule of the existing t = 3 and t = 5 generation kernels.
+template <int AUX = kNt>
+__device__ __forceinline__ void store_fe_at(rsrc_t r, uint32_t o4, uint32_t o2, const uint32_t v[kLimbs]) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) __builtin_amdgcn_raw_buffer_store_b32(v[i], r, o4, i * 4 * kTile, AUX);
+  __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(v[16]), r, o2, static_cast<int>(kHiOffset), AUX);
+}
+template <int AUX = kNt>
+__device__ __forceinline__ void store_reduced_at(rsrc_t r, uint32_t o4, uint32_t o2, uint32_t D[kLimbs]) {
+  const uint32_t hi = D[16] >> 9;
+  const uint32_t top = D[16] & kTopMask;
+  unsigned c;
+  const uint32_t l0 = __builtin_addc(D[0], hi, 0u, &c);
+  const bool rare = (c != 0u) || (top == kTopMask);
+  if (__builtin_expect(__ballot(rare) != 0ull, 0)) {
+    reduce(D);
+    store_fe_at<AUX>(r, o4, o2, D);
+  } else {
+    __builtin_amdgcn_raw_buffer_store_b32(l0, r, o4, 0, AUX);
+#pragma unroll
+    for (int i = 1; i < 16; ++i) __builtin_amdgcn_raw_buffer_store_b32(D[i], r, o4, i * 4 * kTile, AUX);
+    __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(top), r, o2, static_cast<int>(kHiOffset), AUX);
+  }
+}
+
 // v = src * x + c   (x < 2^16, caller guarantees the result < 2^544).
 // Product limbs come from a v_mad_u64_u32 chain whose 64-bit addend carries
 // only the previous high word; c is added by a separate v_addc chain.  (Folding

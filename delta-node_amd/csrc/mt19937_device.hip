@@ -25,6 +25,9 @@
 //    the element it belongs to (T = t, the fused draw + split); one extra
 //    wave steps the last window before CPython's final array to it, so
 //    self.random continues exactly as after n sequential make_shares calls.
+//    The fused form also takes a LIST of tensors (dn_mt19937_split_many_device):
+//    the draw of their concatenation, each tensor's shares stored into its own
+//    block (the SEG kernels, emit_split_seg; seg_plan.hpp).
 // A rejected draw (probability ~2^-520 per coefficient) shifts every later
 // word; the device flags it and the caller redoes the draw on the host.
 #include <hip/hip_runtime.h>
@@ -39,6 +42,7 @@
 
 #include "dn_internal.hpp"
 #include "m521_device.hpp"
+#include "seg_plan.hpp"
 
 namespace dn {
 namespace {
@@ -643,7 +647,11 @@ struct GenArgs {
   uint8_t* coeffs;       // tm1 tiled vectors
   uint32_t* flag;        // != 0: a draw was rejected
   uint32_t* fin;         // CPython's final array (the final-state wave)
-  uint64_t ncoef, vb;
+  uint64_t ncoef;
+  union {
+    uint64_t vb;
+    uint64_t nseg;  // SEG kernels: entries of `segs` before its sentinel
+  };
   uint64_t sub_draws;    // draws per substream (2^k)
   uint64_t tm1_magic;    // ceil(2^32 / tm1): x / tm1 = (x * magic) >> 32 for x < 2^16
   uint32_t S;            // substreams
@@ -653,8 +661,15 @@ struct GenArgs {
   uint64_t final_pos;    // position of that window's first word (0: the caller's array)
   uint64_t final_tf;     // position of CPython's final array
   // fused split (mt_gen_kernel<T>, T > 0): int64 secrets in, n share vectors out
+  // SEG kernels (dn_mt19937_split_many_device): `secrets` is the concatenation
+  // of a list of tensors, n_elem their total, and in place of one share block
+  // and its pitch the kernel gets the tensors' blocks (seg_plan.hpp) — in a
+  // union, so the argument block of the other kernels is what it was
   const int64_t* secrets;
-  uint8_t* shares;
+  union {
+    uint8_t* shares;
+    const SegEnt* segs;
+  };
   uint64_t n_elem;
   int32_t n_shares;
   uint32_t ring;         // ring slots of one wave (2 emission groups; GenRing)
@@ -1024,6 +1039,49 @@ __device__ __forceinline__ void emit_prepare(const GenArgs& a, const uint32_t* r
   fd_init<T>(c);
 }
 
+// The segment table of a SEG kernel, as a pointer into the constant address
+// space: the host wrote it before the launch and no kernel writes it, so its
+// entries come by scalar loads (a uniform index, SGPR results: wave-uniform
+// descriptors without a waterfall loop, and no vector load queued behind the
+// share stores in flight).
+typedef const __attribute__((address_space(4))) SegEnt* SegTab;
+__device__ __forceinline__ SegTab seg_table(const GenArgs& a) { return (SegTab)a.segs; }
+
+__device__ __forceinline__ uint64_t uniform64(uint64_t x) {  // a wave-uniform value, into SGPRs
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(x >> 32));
+  return static_cast<uint64_t>(hi) << 32 | lo;
+}
+
+// A group that is not one tile of one share block (SEG only): per share, one
+// pass over the segments [k, ...) that intersect the group — a wave-uniform
+// loop, one iteration per segment (64 for a group of one-element tensors) —
+// each storing its lanes through one scalar descriptor per share row, based at
+// the row's first touched tile and clamped to the row's end; a lane adds only
+// its offset (one tile's bytes more once it has crossed into the next tile).
+template <int T, int SAUX>
+__device__ __forceinline__ void emit_pieces(const GenArgs& a, uint32_t k0, uint64_t ebase, uint32_t lane, int32_t ns,
+                                            uint32_t (&c)[T][kLimbs]) {
+  const uint64_t gend = a.n_elem - ebase < 64u ? a.n_elem : ebase + 64u;
+  const SegTab tab = seg_table(a);
+#pragma unroll 1
+  for (int32_t xi = 0; xi < ns; ++xi) {
+#pragma unroll 1
+    for (uint32_t k = k0; tab[k].e_begin < gend; ++k) {  // (the sentinel's n_total >= gend ends it)
+      const SegEnt sg{tab[k].e_begin, tab[k].shares, tab[k].row_bytes};
+      const SegPiece p = seg_piece(sg.e_begin, tab[k + 1u].e_begin, sg.row_bytes, ebase, a.n_elem);
+      const uint8_t* base = sg.shares + static_cast<uint64_t>(xi) * sg.row_bytes + p.tile0 * kTileBytes;
+      const rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, static_cast<int>(p.range),
+                                                         0x00020000);
+      if (lane >= p.lane_lo && lane < p.lane_hi) {
+        const uint32_t w = p.w0 + lane - p.lane_lo;
+        store_reduced_at<SAUX>(r, seg_voff32(w), seg_voff16(w), c[0]);
+      }
+    }
+    fd_step<T>(c);
+  }
+}
+
 template <int T, int SAUX, int NS, bool WHOLE>
 __device__ __forceinline__ void emit_split(const GenArgs& a, const uint32_t* rb, uint64_t ebase, uint32_t lane,
                                            uint64_t s, bool mid = false) {
@@ -1052,11 +1110,54 @@ __device__ __forceinline__ void emit_split(const GenArgs& a, const uint32_t* rb,
   }
 }
 
+// emit_split where the elements are the concatenation of a list of tensors,
+// each with a share block of its own (a.segs; SEG kernels).  `seg` is the
+// wave's cursor into the table, moved here to the segment of the group's first
+// element.  A group inside one segment that starts at a multiple of 64 is one
+// tile of that segment's block: emit_split's stores from the segment's base
+// and pitch.  Any other group goes segment by segment (emit_pieces).
+template <int T, int SAUX, int NS, bool WHOLE>
+__device__ __forceinline__ void emit_split_seg(const GenArgs& a, const uint32_t* rb, uint64_t ebase, uint32_t lane,
+                                               uint64_t s, uint32_t& seg, bool mid = false) {
+  const uint64_t e = ebase + lane;
+  if (!WHOLE && e >= a.n_elem) return;
+  // (the table's scalar loads before the ring reads and the tempering)
+  const uint64_t eb = uniform64(ebase);
+  const SegTab tab = seg_table(a);
+  seg = __builtin_amdgcn_readfirstlane(seg_step(tab, seg, eb));
+  const SegEnt sg{tab[seg].e_begin, tab[seg].shares, tab[seg].row_bytes};
+  const uint64_t seg_next = tab[seg + 1u].e_begin;
+  uint32_t c[T][kLimbs];
+  emit_prepare<T>(a, rb, lane, s, c, mid);
+  if (!seg_single_tile(sg.e_begin, seg_next, eb, a.n_elem)) {
+    emit_pieces<T, SAUX>(a, seg, eb, lane, NS > 0 ? NS : a.n_shares, c);
+    return;
+  }
+  const uint64_t l0 = eb - sg.e_begin;  // a multiple of 64: the lanes stay in its tile
+  const uint32_t tile = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(l0 >> 8));
+  const uint32_t wl = (static_cast<uint32_t>(l0) & 255u) + lane;
+  if constexpr (NS > 0) {
+#pragma unroll
+    for (int xi = 1; xi <= NS; ++xi) {
+      store_reduced<SAUX>(tile_rsrc(tile_base(sg.shares + static_cast<uint64_t>(xi - 1) * sg.row_bytes, tile)), wl,
+                          c[0]);
+      if (xi < NS) fd_step<T>(c);
+    }
+  } else {
+#pragma unroll 1
+    for (int32_t xi = 1; xi <= a.n_shares; ++xi) {
+      store_reduced<SAUX>(tile_rsrc(tile_base(sg.shares + static_cast<uint64_t>(xi - 1) * sg.row_bytes, tile)), wl,
+                          c[0]);
+      fd_step<T>(c);
+    }
+  }
+}
+
 // One 64-thread workgroup per substream (one extra for CPython's final state):
 // T == 0 stores the coefficients (groups of 64 draws), T > 0 splits the
 // substream's elements (groups of 64 elements) with them as they are drawn.
 // Dynamic LDS: 1 + ring + 64 words (GenRing).
-template <int T, int SAUX = kNt, int NS = 0>
+template <int T, int SAUX = kNt, int NS = 0, bool SEG = false>
 __global__ void __launch_bounds__(64) mt_gen_kernel(const GenArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t s_ring[];
   const uint32_t lane = threadIdx.x & 63u;
@@ -1094,6 +1195,13 @@ __global__ void __launch_bounds__(64) mt_gen_kernel(const GenArgs a) {
   const uint32_t rbm = static_cast<uint32_t>(k0 - qb * static_cast<uint64_t>(a.tm1));
   constexpr int kRun = 17 * (T ? T - 1 : 1);  // appends per run = one group's words / 64
   static_assert(kRun > 10, "a group holds the 640 words under the window");
+  // SEG: the segment of the first group emitted (the substream's top group
+  // when it runs backward); emit_split steps the cursor from there
+  [[maybe_unused]] uint32_t seg = 0u;
+  if constexpr (SEG && T > 0) {
+    const uint64_t efirst = uniform64(fwd ? qb : qb + 64u * (ngroups - 1u));
+    seg = __builtin_amdgcn_readfirstlane(seg_find(seg_table(a), static_cast<uint32_t>(a.nseg), efirst));
+  }
   if (!fwd) {
     // Backward: whole groups, all inside the vector (never the last
     // substream), last group first; group gi sits in ring half gi % 2
@@ -1125,12 +1233,18 @@ __global__ void __launch_bounds__(64) mt_gen_kernel(const GenArgs a) {
         wave_sync();
         nxt = secret_of(gi ? gi - 1u : 0u);
         DN_PROBE_SKIP(a, 1u)
-        emit_split<T, SAUX, NS, true>(a, R + (gi & 1u) * group, qb + 64u * gi, lane, cur);
+        if constexpr (SEG)
+          emit_split_seg<T, SAUX, NS, true>(a, R + (gi & 1u) * group, qb + 64u * gi, lane, cur, seg);
+        else
+          emit_split<T, SAUX, NS, true>(a, R + (gi & 1u) * group, qb + 64u * gi, lane, cur);
         wave_sync();
       };
       uint64_t secA = secret_of(ngroups - 1u), secB = secret_of(ngroups - 2u);
       DN_PROBE_SKIP(a, 1u)
-      emit_split<T, SAUX, NS, true>(a, R + group, qb + 64u * (ngroups - 1u), lane, secA);
+      if constexpr (SEG)
+        emit_split_seg<T, SAUX, NS, true>(a, R + group, qb + 64u * (ngroups - 1u), lane, secA, seg);
+      else
+        emit_split<T, SAUX, NS, true>(a, R + group, qb + 64u * (ngroups - 1u), lane, secA);
       wave_sync();
       for (uint32_t gi = ngroups - 2u;; gi -= 2u) {
         bstep(gi, secB, secA);
@@ -1178,7 +1292,10 @@ __global__ void __launch_bounds__(64) mt_gen_kernel(const GenArgs a) {
       wave_sync();
       nxt = secret_of(gi + 1u);
       DN_PROBE_SKIP(a, 1u)
-      emit_split<T, SAUX, NS, true>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, cur);
+      if constexpr (SEG)
+        emit_split_seg<T, SAUX, NS, true>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, cur, seg);
+      else
+        emit_split<T, SAUX, NS, true>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, cur);
       wave_sync();
     };
     uint64_t secA = secret_of(0), secB = 0;
@@ -1198,7 +1315,11 @@ __global__ void __launch_bounds__(64) mt_gen_kernel(const GenArgs a) {
     if (gi < ngroups) {  // the vector's last, partial group
       ring_run<kRun>(R, g, slot, lane);
       wave_sync();
-      emit_split<T, SAUX, NS, false>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, secret_of(gi));
+      if constexpr (SEG)
+        emit_split_seg<T, SAUX, NS, false>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane,
+                                           secret_of(gi), seg);
+      else
+        emit_split<T, SAUX, NS, false>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, secret_of(gi));
     }
     asm volatile("" : : "v"(secA ^ secB));  // no load left in flight at the end
     if (a.tail_fin && sub + 1u == a.S) {
@@ -1223,7 +1344,7 @@ __global__ void __launch_bounds__(64) mt_gen_kernel(const GenArgs a) {
 // stores the tempered draws instead of splitting).
 // Dynamic LDS as mt_gen_kernel; registers for 4 waves per SIMD (8 workgroups
 // per CU, the most the rings' LDS allows at t <= 3), 2 at t = 5 (4 fit).
-template <int T, int SAUX = kNt, int NS = 0>
+template <int T, int SAUX = kNt, int NS = 0, bool SEG = false>
 __global__ void __launch_bounds__(128, T == 5 ? 2 : 4) mt_gen_pc_kernel(const GenArgs a) {
   static_assert(T == 0 || T >= 2, "coefficient draw or fused split");
   extern __shared__ __attribute__((aligned(16))) uint32_t s_ring[];
@@ -1261,6 +1382,11 @@ __global__ void __launch_bounds__(128, T == 5 ? 2 : 4) mt_gen_pc_kernel(const Ge
   constexpr int kRun = 17 * (T ? T - 1 : 1);
   static_assert(kRun > 10, "a group holds the 640 words under the window");
   const bool prod = wid == 1u;
+  [[maybe_unused]] uint32_t seg = 0u;  // SEG: the consumer's segment cursor (as mt_gen_kernel)
+  if constexpr (SEG && T > 0) {
+    const uint64_t efirst = uniform64(fwd ? qb : qb + 64u * (ngroups - 1u));
+    if (!prod) seg = __builtin_amdgcn_readfirstlane(seg_find(seg_table(a), static_cast<uint32_t>(a.nseg), efirst));
+  }
   // The two waves run separate loops with the same number of barriers (one
   // per step, ngroups + 1 steps), so the consumer's secrets stay in two
   // registers by group parity as in mt_gen_kernel: no copy of a pending load
@@ -1299,7 +1425,10 @@ __global__ void __launch_bounds__(128, T == 5 ? 2 : 4) mt_gen_pc_kernel(const Ge
     auto bstep = [&](uint32_t gi, uint64_t cur, uint64_t& nxt) {
       nxt = secret_of(gi ? gi - 1u : 0u);
       DN_PROBE_SKIP(a, 1u)
-      emit_split<T, SAUX, NS, true>(a, R + (gi & 1u) * group, qb + 64u * gi, lane, cur);
+      if constexpr (SEG)
+        emit_split_seg<T, SAUX, NS, true>(a, R + (gi & 1u) * group, qb + 64u * gi, lane, cur, seg);
+      else
+        emit_split<T, SAUX, NS, true>(a, R + (gi & 1u) * group, qb + 64u * gi, lane, cur);
       pc_barrier();
     };
     uint64_t secA = secret_of(ngroups - 1u), secB = 0;
@@ -1365,10 +1494,15 @@ __global__ void __launch_bounds__(128, T == 5 ? 2 : 4) mt_gen_pc_kernel(const Ge
   const uint32_t nfull = rem >= 64ull * ngroups ? ngroups : static_cast<uint32_t>(rem / 64u);
   auto cstep = [&](uint32_t gi, uint64_t cur, uint64_t& nxt) {
     nxt = secret_of(gi + 1u);
-    if (!skip_emit)
-      emit_split<T, SAUX, NS, true>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, cur, mid);
-    else if (mid)
+    if (!skip_emit) {
+      if constexpr (SEG)
+        emit_split_seg<T, SAUX, NS, true>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, cur, seg,
+                                          mid);
+      else
+        emit_split<T, SAUX, NS, true>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, cur, mid);
+    } else if (mid) {
       pc_barrier();
+    }
     pc_barrier();
   };
   uint64_t secA = secret_of(0), secB = 0;
@@ -1384,8 +1518,12 @@ __global__ void __launch_bounds__(128, T == 5 ? 2 : 4) mt_gen_pc_kernel(const Ge
     ++gi;
   }
   if (gi < ngroups) {  // the vector's last, partial group
-    emit_split<T, SAUX, NS, false>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, secret_of(gi),
-                                   mid);
+    if constexpr (SEG)
+      emit_split_seg<T, SAUX, NS, false>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, secret_of(gi),
+                                         seg, mid);
+    else
+      emit_split<T, SAUX, NS, false>(a, R + g.o + g.delta + (gi & 1u) * group, qb + 64u * gi, lane, secret_of(gi),
+                                     mid);
     pc_barrier();
   }
   asm volatile("" : : "v"(secA ^ secB));
@@ -2385,14 +2523,15 @@ constexpr int kSc1 = DN_MT_SAUX;
 #define DN_MT_PC 1
 #endif  // buffer-store cache policy of the 3-of-5 share stores: sc1 (16)
 
-template <int T>
+// SEG: the segmented emission (ga.segs; dn_mt19937_split_many_device)
+template <int T, bool SEG = false>
 void launch_gen(GenArgs& ga, hipStream_t s) {
   ga.ring = 2u * 17u * 64u * (T ? T - 1 : 1);
   const uint32_t lds_words = 1u + ga.ring + 64u;  // GenRing: alignment word, ring, mirror
 #ifdef DN_TUNING
   // DN_MT_STORE_AUX (tuning build): cache policy bits of the fused split's share stores (3-of-5)
   const char* sa = T == 3 ? tune_env("DN_MT_STORE_AUX") : nullptr;
-  if (sa && T == 3 && ga.n_shares == 5) {
+  if (sa && T == 3 && ga.n_shares == 5 && !SEG) {
     const int aux = std::atoi(sa);
     constexpr int NS = T == 3 ? 5 : 0;
     const dim3 g(ga.S + 1), b(64);
@@ -2422,17 +2561,18 @@ void launch_gen(GenArgs& ga, hipStream_t s) {
     if (const char* gs = tune_env("DN_MT_GEN_SUBS")) grid = std::min<uint32_t>(grid, std::max(1, std::atoi(gs)));
     if (pc) {
       if (T == 3 && ga.n_shares == 5)
-        hipLaunchKernelGGL((mt_gen_pc_kernel<T, kSc1, T == 3 ? 5 : 0>), dim3(grid), dim3(128), lds_words * 4u, s, ga);
+        hipLaunchKernelGGL((mt_gen_pc_kernel<T, kSc1, T == 3 ? 5 : 0, SEG>), dim3(grid), dim3(128), lds_words * 4u, s,
+                           ga);
       else
-        hipLaunchKernelGGL((mt_gen_pc_kernel<T>), dim3(grid), dim3(128), lds_words * 4u, s, ga);
+        hipLaunchKernelGGL((mt_gen_pc_kernel<T, kNt, 0, SEG>), dim3(grid), dim3(128), lds_words * 4u, s, ga);
       return;
     }
   }
   const dim3 g1(ga.sub_n ? ga.sub_n : ga.S + 1);
   if (T == 3 && ga.n_shares == 5)
-    hipLaunchKernelGGL((mt_gen_kernel<T, kSc1, T == 3 ? 5 : 0>), g1, dim3(64), lds_words * 4u, s, ga);
+    hipLaunchKernelGGL((mt_gen_kernel<T, kSc1, T == 3 ? 5 : 0, SEG>), g1, dim3(64), lds_words * 4u, s, ga);
   else
-    hipLaunchKernelGGL((mt_gen_kernel<T>), g1, dim3(64), lds_words * 4u, s, ga);
+    hipLaunchKernelGGL((mt_gen_kernel<T, kNt, 0, SEG>), g1, dim3(64), lds_words * 4u, s, ga);
 }
 
 }  // namespace
@@ -2477,6 +2617,87 @@ extern "C" int dn_mt19937_split_device(uint32_t* mt_state, int32_t* mt_index, co
                          else if (threshold == 3) launch_gen<3>(ga, s);
                          else launch_gen<5>(ga, s);
                        });
+}
+
+// ---- one fused draw + split over a list of tensors ---------------------------
+// make_shares draws every coefficient from one sequential stream
+// (shamir.py:59-61), so splitting tensors A, B, C in turn draws the words one
+// split of concat(A, B, C) draws: the draw runs as for one vector of n_total
+// elements (same levels, substreams, speculation), and only the emission
+// differs — each tensor's shares go to that tensor's own tiled block
+// (emit_split_seg, seg_plan.hpp).  The segment table sits behind the draw's
+// own scratch, uploaded from a pinned buffer on the caller's stream.
+extern "C" uint64_t dn_mt19937_split_many_scratch_bytes(uint64_t n_total, int tm1, uint64_t n_segments) {
+  return dn_mt19937_device_scratch_bytes(n_total, tm1) + (n_segments + 1) * sizeof(SegEnt);
+}
+
+extern "C" int dn_mt19937_split_many_supported(uint64_t n_total, int threshold, int n_shares, uint64_t n_segments) {
+  return n_segments <= kMaxSegments && dn_mt19937_split_supported(n_total, threshold, n_shares);
+}
+
+extern "C" int dn_mt19937_split_many_device(uint32_t* mt_state, int32_t* mt_index, const int64_t* secrets,
+                                            const dn_m521_segment_t* segments, uint64_t n_segments, int threshold,
+                                            int n_shares, void* scratch, uint64_t scratch_bytes, void* stream) {
+  const char* name = "dn_mt19937_split_many_device";
+  if (threshold < 1 || threshold > DN_MAX_THRESHOLD)
+    return set_error(DN_ERR_UNSUPPORTED, "%s: threshold %d outside 1..%d", name, threshold, DN_MAX_THRESHOLD);
+  if (threshold > n_shares) return set_error(DN_ERR_THRESHOLD, "threshold should be little equal than shares");
+  if (!(threshold == 2 || threshold == 3 || threshold == 5) || fd_needs_fold(threshold, n_shares) ||
+      n_shares > DN_MAX_SHARES)
+    return set_error(DN_ERR_UNSUPPORTED, "%s: fused form needs t in {2, 3, 5} and forward differences (t=%d, n=%d)",
+                     name, threshold, n_shares);
+  if (n_segments > kMaxSegments)
+    return set_error(DN_ERR_ARG, "%s: %llu segments (at most %llu)", name, static_cast<unsigned long long>(n_segments),
+                     static_cast<unsigned long long>(kMaxSegments));
+  if (n_segments && !segments) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+  uint64_t n_total = 0, nseg = 0;
+  for (uint64_t k = 0; k < n_segments; ++k) {
+    if (!segments[k].n_elem) continue;  // an empty tensor consumes no draw
+    if (!segments[k].shares) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+    n_total += segments[k].n_elem;
+    ++nseg;
+  }
+  if (!mt_state || !mt_index) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+  if (!n_total) return DN_OK;
+  if (!secrets || !scratch) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+  const int tm1 = threshold - 1;
+  if (!dn_mt19937_split_supported(n_total, threshold, n_shares))
+    return set_error(DN_ERR_UNSUPPORTED, "%s: %llu words exceed the jump table", name,
+                     static_cast<unsigned long long>(17 * n_total * static_cast<uint64_t>(tm1)));
+  const uint64_t draw_bytes = dn_mt19937_device_scratch_bytes(n_total, tm1);
+  if (scratch_bytes < dn_mt19937_split_many_scratch_bytes(n_total, tm1, n_segments))
+    return set_error(DN_ERR_ARG, "%s: scratch too small", name);
+  const size_t tab_bytes = (nseg + 1) * sizeof(SegEnt);
+  PinLease tab((tab_bytes + 3) / 4);  // idle again once the stream has been synchronised (below, on every path)
+  if (!tab.p) return set_error(DN_ERR_HIP, "%s: pinned staging buffer", name);
+  SegEnt* ent = reinterpret_cast<SegEnt*>(tab.p);
+  uint64_t e = 0, j = 0;
+  for (uint64_t k = 0; k < n_segments; ++k) {
+    if (!segments[k].n_elem) continue;
+    ent[j++] = SegEnt{e, static_cast<uint8_t*>(segments[k].shares), dn_m521_vec_bytes(segments[k].n_elem)};
+    e += segments[k].n_elem;
+  }
+  ent[j] = SegEnt{n_total, nullptr, 0};
+  SegEnt* dtab = reinterpret_cast<SegEnt*>(static_cast<uint8_t*>(scratch) + draw_bytes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemcpyAsync(dtab, ent, tab_bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    return set_error(DN_ERR_HIP, "%s: segment table upload", name);
+  }
+  const int rc = mt_device_run(name, mt_state, mt_index, n_total, tm1, scratch, draw_bytes, stream, tm1,
+                               [&](GenArgs& ga, hipStream_t s) {
+                                 ga.secrets = secrets;
+                                 ga.n_shares = n_shares;
+                                 ga.segs = dtab;
+                                 ga.nseg = nseg;  // (after mt_device_run's ga.vb: the same storage)
+                                 if (threshold == 2) launch_gen<2, true>(ga, s);
+                                 else if (threshold == 3) launch_gen<3, true>(ga, s);
+                                 else launch_gen<5, true>(ga, s);
+                               });
+  // the draw synchronises the stream before DN_OK and DN_ERR_RETRY; an
+  // argument error may return before it, with the table's copy in flight
+  if (rc != DN_OK && rc != DN_ERR_RETRY) (void)hipStreamSynchronize(st);
+  return rc;
 }
 
 // The current device's speculation counters (DN_MT_SPEC): out[0] calls that

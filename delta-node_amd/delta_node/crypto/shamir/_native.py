@@ -49,6 +49,7 @@ EXPORTS = (
     "dn_shamir_eval_at_host", "dn_block_granularity", "dn_block_alloc", "dn_block_free", "dn_block_probe_rows",
     "dn_block_record", "dn_block_ready", "dn_block_acquire", "dn_block_retired_bytes",
     "dn_mt19937_rt_rows_embedded", "dn_mt19937_spec_stats", "dn_mt19937_jump_poly",
+    "dn_mt19937_split_many_scratch_bytes", "dn_mt19937_split_many_supported", "dn_mt19937_split_many_device",
 )
 
 
@@ -70,6 +71,12 @@ class Lagrange(ctypes.Structure):
         ("w", ctypes.c_uint32 * 17),
         ("reserved", ctypes.c_uint32),
     ]
+
+
+class Segment(ctypes.Structure):
+    """Mirror of dn_m521_segment_t."""
+
+    _fields_ = [("n_elem", ctypes.c_uint64), ("shares", ctypes.c_void_p)]
 
 
 _lock = threading.Lock()
@@ -175,6 +182,13 @@ def _load(path: str) -> ctypes.CDLL:
     if hasattr(L, "dn_mt19937_jump_poly"):
         L.dn_mt19937_jump_poly.restype = i32
         L.dn_mt19937_jump_poly.argtypes = [u64, ctypes.POINTER(u64)]
+    if hasattr(L, "dn_mt19937_split_many_device"):
+        L.dn_mt19937_split_many_scratch_bytes.restype = u64
+        L.dn_mt19937_split_many_scratch_bytes.argtypes = [u64, i32, u64]
+        L.dn_mt19937_split_many_supported.restype = i32
+        L.dn_mt19937_split_many_supported.argtypes = [u64, i32, i32, u64]
+        L.dn_mt19937_split_many_device.restype = i32
+        L.dn_mt19937_split_many_device.argtypes = [vp, vp, vp, ctypes.POINTER(Segment), u64, i32, i32, vp, u64, vp]
     L.dn_block_retired_bytes.restype = i32
     L.dn_block_retired_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.dn_block_probe_rows.restype = i32
@@ -519,6 +533,57 @@ def mt_split_device(rng, secrets, shares, n: int, t: int, n_shares: int) -> bool
         version, gauss, state, index = _mt_state(rng)
         rc = L.dn_mt19937_split_device(ctypes.addressof(state), ctypes.addressof(index), secrets.data_ptr(),
                                        shares.data_ptr(), n, t, n_shares, scratch.data_ptr(), sb, stream_ptr())
+    if rc in (DN_ERR_RETRY, DN_ERR_UNSUPPORTED):
+        return False
+    check(rc)
+    if not ip:
+        _mt_set_state(rng, version, gauss, state, index)
+    return True
+
+
+_MT_MANY_SHAPES: dict = {}  # (library, n_total, t, n_shares, segments) -> (supported, scratch bytes)
+
+
+def mt_split_many_device(rng, secrets, segs, t: int, n_shares: int) -> bool:
+    """`mt_split_device` over a list of tensors in one fused draw + split
+    (dn_mt19937_split_many_device): `secrets` the tensors' int64 elements
+    concatenated on the device, `segs` one (n_k, shares_k) per tensor with
+    shares_k the device address of a contiguous uint8 [n_shares,
+    vec_bytes(n_k)] block on the secrets' device (ignored where n_k == 0; the
+    caller has validated its tensors: a model's hundred tensors are not walked
+    twice).  Same results and final `rng` state as mt_split_device on each
+    tensor in turn.  False (rng untouched, shares unspecified) when the fused
+    form does not apply or a draw was rejected."""
+    n_total = sum(n for n, _ in segs)
+    if n_total == 0:
+        return True
+    L = lib()
+    if not hasattr(L, "dn_mt19937_split_many_device"):
+        raise RuntimeError(f"{lib_path()} lacks dn_mt19937_split_many_device: rebuild the native library")
+    key = (id(L), n_total, t, n_shares, len(segs))
+    shape = _MT_MANY_SHAPES.get(key)
+    if shape is None:
+        sup = bool(L.dn_mt19937_split_many_supported(n_total, t, n_shares, len(segs)))
+        shape = (sup, int(L.dn_mt19937_split_many_scratch_bytes(n_total, t - 1, len(segs))) if sup else 0)
+        if len(_MT_MANY_SHAPES) >= 256:
+            _MT_MANY_SHAPES.clear()
+        _MT_MANY_SHAPES[key] = shape
+    if not shape[0]:
+        return False  # before any allocation: the per-tensor calls
+    dev = secrets.device
+    if not secrets.is_cuda or not secrets.is_contiguous() or secrets.numel() != n_total:
+        raise ValueError("mt_split_many_device: secrets must be a contiguous device tensor of the tensors' elements")
+    table = (Segment * len(segs))(*segs)
+    sb = shape[1]
+    scratch = _mt_scratch(sb, dev)
+    ip = _mt_inplace_addr(rng)  # the entry point writes the state only on success
+    if ip:
+        rc = L.dn_mt19937_split_many_device(ip[0], ip[1], secrets.data_ptr(), table, len(segs), t, n_shares,
+                                            scratch.data_ptr(), sb, stream_ptr())
+    else:
+        version, gauss, state, index = _mt_state(rng)
+        rc = L.dn_mt19937_split_many_device(ctypes.addressof(state), ctypes.addressof(index), secrets.data_ptr(),
+                                            table, len(segs), t, n_shares, scratch.data_ptr(), sb, stream_ptr())
     if rc in (DN_ERR_RETRY, DN_ERR_UNSUPPORTED):
         return False
     check(rc)

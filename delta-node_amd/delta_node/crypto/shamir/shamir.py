@@ -89,6 +89,24 @@ def _device_values(values, dev, name: str):
     return vals.reshape(-1).to(dev).contiguous()
 
 
+def _concat_values(vals: Sequence):
+    """The concatenation of contiguous 1-D int64 device tensors (at least one
+    non-empty) as one such tensor: the tensors' own memory when they lie back
+    to back in one buffer (a model kept as views of one flat parameter
+    vector), else one torch.cat on the device."""
+    import torch
+
+    live = [v for v in vals if v.numel()]
+    if len(live) == 1:
+        return live[0]
+    base, end = live[0].untyped_storage().data_ptr(), live[0].data_ptr()
+    for v in live:
+        if v.untyped_storage().data_ptr() != base or v.data_ptr() != end:
+            return torch.cat(live)
+        end += 8 * v.numel()
+    return torch.as_strided(live[0], (sum(v.numel() for v in live),), (1,))
+
+
 def _eval_many(coeffs: Sequence[int], n_shares: int) -> List[int]:
     """y(x) = sum_j coeffs[j] x^j mod p for x = 1..n_shares, on the GPU.
     coeffs[0] is the secret (any size; reduced mod p here)."""
@@ -320,6 +338,70 @@ class SecretShare(object):
         if shares > 0:
             _native.split_u64(vals, coeffs if t > 1 else None, out, n, t, shares)
         return out
+
+    def make_shares_vec_many(self, tensors, shares: int, *, outs=None) -> list:
+        """`[self.make_shares_vec(x, shares) for x in tensors]` in one fused
+        draw + split — the runner's walk over a model's tensors
+        (runner/horizontal/agg.py:294-316) as one call.
+
+        make_shares draws every coefficient from one sequential stream
+        (shamir.py:59-61), so the per-tensor calls draw exactly the words one
+        split of the tensors' concatenation draws: the results, element for
+        element, and the final `self.random.getstate()` are identical.
+
+        tensors  sequence of int64 tensors (any shape and device; each read
+                 flattened in C order, as make_shares_vec reads one)
+        outs     optional list of uint8 device tensors, outs[k] contiguous
+                 [shares, vec_bytes(n_k)]; default: contiguous views of ONE
+                 pooled block (memory.share_block) of shares * sum
+                 vec_bytes(n_k) bytes, reused as a whole
+        Returns one uint8 device tensor [shares, vec_bytes(n_k)] per input, in
+        order ([shares, 0] for an empty one).
+
+        The secrets go to the kernel as one int64 vector: the inputs' own
+        buffer when they are consecutive views of one contiguous device
+        buffer, else one torch.cat on the device (16 B per element against
+        338 B of share traffic at 3-of-5).  Where the fused form does not
+        apply (a generator that is not plain MT19937, t not in {2, 3, 5}, a
+        stream beyond the jump table, a rejected draw) the per-tensor
+        make_shares_vec loop runs into the same outputs."""
+        self._require_m521()
+        import torch
+
+        if self.threshold > shares:
+            raise ValueError("threshold should be little equal than shares")
+        if shares > _native.MAX_SHARES or self.threshold > _native.MAX_THRESHOLD:
+            raise NotImplementedError("make_shares_vec_many: at most 65535 shares and threshold 64")
+        dev = _device()
+        vals = [_device_values(x, dev, "make_shares_vec_many") for x in tensors]
+        ns = [v.numel() for v in vals]
+        vbs = [field.vec_bytes(n) for n in ns]
+        t = max(self.threshold, 1)
+        rows = max(shares, 0)
+        if outs is None:
+            blk = memory.share_block((rows * sum(vbs),), dev)
+            parts = torch.split(blk, [rows * vb for vb in vbs]) if vbs else ()
+            outs = [p.view(rows, vb) for p, vb in zip(parts, vbs)]
+            ptrs, off = [], blk.data_ptr()
+            for vb in vbs:
+                ptrs.append(off)
+                off += rows * vb
+        else:
+            outs = list(outs)
+            if len(outs) != len(vals):
+                raise ValueError(f"make_shares_vec_many: {len(outs)} outs for {len(vals)} tensors")
+            for out, vb in zip(outs, vbs):
+                if (out.dtype != torch.uint8 or tuple(out.shape) != (shares, vb) or not out.is_contiguous()
+                        or out.device != dev):
+                    raise ValueError(f"make_shares_vec_many: out must be contiguous uint8 [{shares}, {vb}] on {dev}")
+            ptrs = [out.data_ptr() for out in outs]
+        if (t in (2, 3, 5) and shares > 0 and sum(ns) > 0 and _native.mt_compatible(self.random)
+                and _native.mt_split_many_device(self.random, _concat_values(vals), list(zip(ns, ptrs)), t, shares)):
+            self.last_draw_rejected = False
+            return outs
+        for v, out in zip(vals, outs):  # the calls this one stands for, into the same outputs
+            self.make_shares_vec(v, shares, out=out)
+        return outs
 
     def make_shares_vec_prng(self, values, shares: int, *, key: Optional[bytes] = None, nonce: int = 0,
                              rounds: int = 20, elem_offset: int = 0, out=None):

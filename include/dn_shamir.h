@@ -226,6 +226,43 @@ int dn_mt19937_split_device(uint32_t* mt_state, int32_t* mt_index, const int64_t
 int dn_mt19937_split_supported(uint64_t n_elem, int threshold, int n_shares);
 
 /*
+ * dn_mt19937_split_device over a LIST of tensors in one fused draw + split.
+ * make_shares draws every coefficient from one sequential stream
+ * (shamir.py:55-66, the draws at :59-61), and the reference's runner walks its
+ * result dict tensor by tensor (runner/horizontal/agg.py:294-316): splitting
+ * tensors 0, 1, 2 ... in turn draws exactly the words one split of their
+ * concatenation draws.  This entry point runs that one draw — the jump levels,
+ * substreams and speculation of a single vector of n_total = sum n_elem
+ * elements — and writes each tensor's shares into that tensor's own block.
+ *   secrets   device int64[n_total]: the tensors' elements, concatenated
+ *   segments  HOST array of n_segments entries; `shares` of entry k is a
+ *             DEVICE block of n_shares tiled vectors of n_elem elements at a
+ *             row pitch of dn_m521_vec_bytes(n_elem).  An entry with n_elem 0
+ *             draws nothing and its `shares` is not read.
+ *   scratch   device memory of dn_mt19937_split_many_scratch_bytes(n_total,
+ *             t-1, n_segments) bytes (the draw's scratch and the segment table)
+ * Results — every block and the final MT state — are those of
+ * dn_mt19937_split_device on segment 0, then segment 1, ... with the same
+ * state and index.  Synchronises `stream`.  Limits and codes as
+ * dn_mt19937_split_device: DN_ERR_UNSUPPORTED (t not in {2, 3, 5}, forward
+ * differences need folding, the stream beyond the jump table) and
+ * DN_ERR_RETRY (a rejected draw) leave the state untouched; DN_ERR_ARG for a
+ * null pointer or more than 65536 segments.
+ * dn_mt19937_split_many_supported: 1 when the call is taken (as
+ * dn_mt19937_split_supported on n_total, and at most 65536 segments), else 0.
+ */
+typedef struct dn_m521_segment {
+  uint64_t n_elem;
+  void* shares;
+} dn_m521_segment_t;
+
+uint64_t dn_mt19937_split_many_scratch_bytes(uint64_t n_total, int tm1, uint64_t n_segments);
+int dn_mt19937_split_many_supported(uint64_t n_total, int threshold, int n_shares, uint64_t n_segments);
+int dn_mt19937_split_many_device(uint32_t* mt_state, int32_t* mt_index, const int64_t* secrets,
+                                 const dn_m521_segment_t* segments, uint64_t n_segments, int threshold,
+                                 int n_shares, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/*
  * Host.  The byte API for one secret per call (csrc/host_shamir.cpp), the way
  * the reference's callers use it (runner/horizontal/agg.py:142-153,
  * coord/horizontal/agg.py:296,330,362), in any prime field (shamir.py:49-51).
