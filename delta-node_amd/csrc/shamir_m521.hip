@@ -20,10 +20,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
+#include <vector>
 
 #include "chacha_device.hpp"
 #include "dn_internal.hpp"
 #include "m521_device.hpp"
+#include "recon_plan.hpp"
 
 namespace dn {
 
@@ -525,8 +528,10 @@ struct ReconArgs {
 // before the first multiply; K == 0: runtime count, one share at a time.
 // S reduced, divided and stored for element w of the tile; returns whether
 // the result is >= 2^64 (the overflow count).
-template <int A, int INV>
-__device__ __forceinline__ bool recon_finish(const ReconArgs& a, uint32_t tile, uint32_t w,
+// o: where the results go — out_fe, out_u64 (either may be null); the single
+// vector's ReconArgs itself, or a segment's table entry.
+template <int A, int INV, typename Out>
+__device__ __forceinline__ bool recon_finish(const ReconArgs& a, const Out& o, uint32_t tile, uint32_t w,
                                              uint32_t (&S)[A + kLimbs]) {
   constexpr int N = A + kLimbs;
   constexpr int VB = (A == kLimbs) ? 1046 : (521 + 32 * A + 4);
@@ -541,10 +546,10 @@ __device__ __forceinline__ bool recon_finish(const ReconArgs& a, uint32_t tile, 
     exact_div_small(r, a.d, a.d_inv32, a.p_inv_d, a.d_recip, a.w);
   }
   if (a.shift != 0u) rotr521(r, a.shift);
-  if (a.out_fe) store_fe(tile_base(a.out_fe, tile), w, r);
-  if (a.out_u64) {
+  if (o.out_fe) store_fe(o.out_fe + recon_tile_offset(tile), w, r);
+  if (o.out_u64) {
     const uint64_t lo = static_cast<uint64_t>(r[0]) | (static_cast<uint64_t>(r[1]) << 32);
-    __builtin_nontemporal_store(static_cast<int64_t>(lo), a.out_u64 + static_cast<uint64_t>(tile) * kTile + w);
+    __builtin_nontemporal_store(static_cast<int64_t>(lo), o.out_u64 + recon_elem(tile, 0u) + w);
   }
   uint32_t hi_or = 0u;
 #pragma unroll
@@ -553,8 +558,9 @@ __device__ __forceinline__ bool recon_finish(const ReconArgs& a, uint32_t tile, 
 }
 
 // One element's S from its K loaded rows (K > 0), then recon_finish.
-template <int A, int INV, int K>
-__device__ __forceinline__ bool recon_rows(const ReconArgs& a, uint32_t tile, uint32_t w, uint32_t (&y)[K][kLimbs]) {
+template <int A, int INV, int K, typename Out>
+__device__ __forceinline__ bool recon_rows(const ReconArgs& a, const Out& o, uint32_t tile, uint32_t w,
+                                           uint32_t (&y)[K][kLimbs]) {
   uint32_t S[A + kLimbs];
 #pragma unroll
   for (int i = 0; i < A + kLimbs; ++i) S[i] = 0u;
@@ -567,7 +573,7 @@ __device__ __forceinline__ bool recon_rows(const ReconArgs& a, uint32_t tile, ui
     }
     mac_wide<A + kLimbs, A>(S, a.a[i], y[i]);
   }
-  return recon_finish<A, INV>(a, tile, w, S);
+  return recon_finish<A, INV>(a, o, tile, w, S);
 }
 
 // DN_RECON_PF (default 1): a wave working a whole tile's four quarters loads
@@ -579,9 +585,81 @@ __device__ __forceinline__ bool recon_rows(const ReconArgs& a, uint32_t tile, ui
 #define DN_RECON_PF 1
 #endif
 
+// One tile of one vector of a list (reconstruct_many_kernel): o holds the
+// vector's n_elem, outputs and overflow counter (recon_finish's Out), `tile`
+// counts within the vector's own rows and outputs, row(i) is share row i's
+// base (wave-uniform), and the weights are a's.  The tile-within-vector
+// arithmetic is recon_plan.hpp's.  This is reconstruct_kernel's loop body;
+// that kernel keeps its own copy below, because calling this one from it
+// changed the scheduling of every existing instantiation.
+template <int A, int INV, int K, typename Out, typename Row>
+__device__ __forceinline__ void recon_tile(const ReconArgs& a, const Out& o, Row row, uint32_t tile,
+                                           const WaveSched& ws, uint32_t lane) {
+  constexpr int N = A + kLimbs;
+#if DN_RECON_PF
+  if constexpr (K > 0) {
+    if (ws.q0 == 0u && ws.q1 == 4u && recon_tile_full(o.n_elem, tile)) {
+      constexpr int D = DN_RECON_PF, B = D + 1;  // quarters loaded ahead, buffers
+      uint32_t y[B][K][kLimbs];
+#pragma unroll
+      for (int p = 0; p < D; ++p)
+#pragma unroll
+        for (int i = 0; i < K; ++i) load_fe(tile_base(row(i), tile), lane + 64u * p, y[p % B][i]);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (q + D < 4) {
+#pragma unroll
+          for (int i = 0; i < K; ++i) load_fe(tile_base(row(i), tile), lane + 64u * (q + D), y[(q + D) % B][i]);
+        }
+        const bool over = recon_rows<A, INV, K>(a, o, tile, lane + 64u * q, y[q % B]);
+        if (o.overflow) {
+          const uint64_t m = __ballot(over);
+          if (lane == 0 && m) atomicAdd(o.overflow, static_cast<uint32_t>(__popcll(m)));
+        }
+      }
+      return;
+    }
+  }
+#endif
+#pragma unroll 1
+  for (uint32_t q = ws.q0; q < ws.q1; ++q) {
+    const uint32_t w = lane + 64u * q;
+    const bool valid = recon_live(o.n_elem, tile, w);
+    bool over = false;
+    if (valid) {
+      if constexpr (K > 0) {
+        uint32_t y[K][kLimbs];
+#pragma unroll
+        for (int i = 0; i < K; ++i) load_fe(tile_base(row(i), tile), w, y[i]);
+        over = recon_rows<A, INV, K>(a, o, tile, w, y);
+      } else {
+        uint32_t S[N];
+#pragma unroll
+        for (int i = 0; i < N; ++i) S[i] = 0u;
+#pragma unroll 1
+        for (int32_t i = 0; i < a.k; ++i) {
+          uint32_t y[kLimbs];
+          load_fe(tile_base(row(i), tile), w, y);
+          if ((a.neg >> i) & 1u) {
+#pragma unroll
+            for (int l = 0; l < 16; ++l) y[l] = ~y[l];
+            y[16] = (~y[16]) & kTopMask;
+          }
+          mac_wide<N, A>(S, a.a[i], y);
+        }
+        over = recon_finish<A, INV>(a, o, tile, w, S);
+      }
+    }
+    if (o.overflow) {
+      const uint64_t m = __ballot(over);
+      if (lane == 0 && m) atomicAdd(o.overflow, static_cast<uint32_t>(__popcll(m)));
+    }
+    if (!valid) break;
+  }
+}
+
 template <int A, int INV, int K>
 __global__ void __launch_bounds__(kBlock) reconstruct_kernel(const ReconArgs a) {
-  constexpr int N = A + kLimbs;
   const uint32_t lane = threadIdx.x & 63u;
   const WaveSched ws = wave_sched(a.tile_map, a.ntiles);
   for (uint32_t tile = ws.first; tile < ws.end; tile += ws.step) {
@@ -601,7 +679,7 @@ __global__ void __launch_bounds__(kBlock) reconstruct_kernel(const ReconArgs a) 
             for (int i = 0; i < K; ++i)
               load_fe(tile_base(a.shares[i], tile), lane + 64u * (q + D), y[(q + D) % B][i]);
           }
-          const bool over = recon_rows<A, INV, K>(a, tile, lane + 64u * q, y[q % B]);
+          const bool over = recon_rows<A, INV, K>(a, a, tile, lane + 64u * q, y[q % B]);
           if (a.overflow) {
             const uint64_t m = __ballot(over);
             if (lane == 0 && m) atomicAdd(a.overflow, static_cast<uint32_t>(__popcll(m)));
@@ -622,8 +700,9 @@ __global__ void __launch_bounds__(kBlock) reconstruct_kernel(const ReconArgs a) 
           uint32_t y[K][kLimbs];
 #pragma unroll
           for (int i = 0; i < K; ++i) load_fe(tile_base(a.shares[i], tile), w, y[i]);
-          over = recon_rows<A, INV, K>(a, tile, w, y);
+          over = recon_rows<A, INV, K>(a, a, tile, w, y);
         } else {
+          constexpr int N = A + kLimbs;
           uint32_t S[N];
 #pragma unroll
           for (int i = 0; i < N; ++i) S[i] = 0u;
@@ -638,7 +717,7 @@ __global__ void __launch_bounds__(kBlock) reconstruct_kernel(const ReconArgs a) 
             }
             mac_wide<N, A>(S, a.a[i], y);
           }
-          over = recon_finish<A, INV>(a, tile, w, S);
+          over = recon_finish<A, INV>(a, a, tile, w, S);
         }
       }
       if (a.overflow) {
@@ -647,6 +726,47 @@ __global__ void __launch_bounds__(kBlock) reconstruct_kernel(const ReconArgs a) 
       }
       if (!valid) break;
     }
+  }
+}
+
+// ---- segmented reconstruct (dn_m521_reconstruct_many) ------------------------
+// reconstruct_kernel over a LIST of vectors in one launch.  The work space is
+// the global tile range of recon_plan.hpp, walked with the same wave_sched; per
+// tile a wave finds its segment (one binary search for its first tile, a
+// forward cursor after that: its tiles only increase), reads that segment's
+// entry and K row bases, and runs recon_tile on the local tile.  Table and row
+// array are read through constant-address-space pointers: the host wrote them
+// before the launch and no kernel writes them, so the entries come by scalar
+// loads and every base stays in SGPRs (no waterfall loop).  The weights (a.r)
+// are the call's, the same for every segment; a.r's shares / outputs / n_elem
+// are unused and a.r.ntiles is the total.
+struct ReconManyArgs {
+  ReconArgs r;
+  const ReconSegEnt* segs;  // nseg entries and the sentinel
+  const uint8_t* const* rows;  // nseg * k share-row bases
+  uint32_t nseg;
+};
+
+typedef const __attribute__((address_space(4))) ReconSegEnt* ReconTab;
+typedef const uint8_t* ReconRow;
+typedef const __attribute__((address_space(4))) ReconRow* ReconRowTab;
+
+template <int A, int INV, int K>
+__global__ void __launch_bounds__(kBlock) reconstruct_many_kernel(const ReconManyArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const WaveSched ws = wave_sched(a.r.tile_map, a.r.ntiles);
+  if (ws.first >= ws.end) return;
+  const ReconTab tab = (ReconTab)a.segs;
+  const ReconRowTab rows = (ReconRowTab)a.rows;
+  const uint32_t k = static_cast<uint32_t>(K > 0 ? K : a.r.k);
+  uint32_t seg = __builtin_amdgcn_readfirstlane(recon_seg_find(tab, a.nseg, ws.first));
+  for (uint32_t tile = ws.first; tile < ws.end; tile += ws.step) {
+    seg = __builtin_amdgcn_readfirstlane(recon_seg_step(tab, seg, tile));
+    const ReconSegEnt e{tab[seg].tile_begin, 0u, tab[seg].n_elem, tab[seg].out_fe, tab[seg].out_u64,
+                        tab[seg].overflow};
+    const ReconRowTab r0 = rows + static_cast<uint64_t>(seg) * k;
+    recon_tile<A, INV, K>(a.r, e, [&](int i) { return r0[i]; }, tile - e.tile_begin,
+                          ws, lane);
   }
 }
 
@@ -670,6 +790,22 @@ static void launch_recon_k(int k, dim3 g, hipStream_t s, const ReconArgs& a) {
     }
   }
   hipLaunchKernelGGL((reconstruct_kernel<A, INV, 0>), g, dim3(kBlock), 0, s, a);
+}
+
+template <int A, int INV>
+static void launch_recon_many_k(int k, dim3 g, hipStream_t s, const ReconManyArgs& a) {
+  if constexpr (A == 1) {
+    if (recon_unroll()) {
+      switch (k) {
+        case 2: hipLaunchKernelGGL((reconstruct_many_kernel<A, INV, 2>), g, dim3(kBlock), 0, s, a); return;
+        case 3: hipLaunchKernelGGL((reconstruct_many_kernel<A, INV, 3>), g, dim3(kBlock), 0, s, a); return;
+        case 4: hipLaunchKernelGGL((reconstruct_many_kernel<A, INV, 4>), g, dim3(kBlock), 0, s, a); return;
+        case 5: hipLaunchKernelGGL((reconstruct_many_kernel<A, INV, 5>), g, dim3(kBlock), 0, s, a); return;
+        default: break;
+      }
+    }
+  }
+  hipLaunchKernelGGL((reconstruct_many_kernel<A, INV, 0>), g, dim3(kBlock), 0, s, a);
 }
 
 // Compute units of the current device (cached per device id).
@@ -857,6 +993,101 @@ static int split_common(SplitArgs a, int threshold, int n_shares, void* stream, 
 
 int device_cu_count() { return cu_count(); }
 
+// The descriptor checks every reconstruct entry point makes before it looks at
+// n_elem, and the ones it makes after (an empty call returns in between).
+static int recon_check_weights(const dn_m521_lagrange_t* w, const char* name) {
+  if (w->k < 1 || w->k > DN_MAX_RESOLVE)
+    return set_error(DN_ERR_UNSUPPORTED, "%s: k=%d outside 1..%d", name, w->k, DN_MAX_RESOLVE);
+  if (!(w->a_limbs == 1 || w->a_limbs == 2 || w->a_limbs == 17) || w->shift < 0 || w->shift > 31)
+    return set_error(DN_ERR_ARG, "%s: malformed weights", name);
+  return DN_OK;
+}
+
+static int recon_set_weights(ReconArgs& a, const dn_m521_lagrange_t* w, const char* name) {
+  a.k = w->k;
+  a.neg = w->neg;
+  a.shift = static_cast<uint32_t>(w->shift);
+  std::memcpy(a.a, w->a, sizeof(a.a));
+  std::memcpy(a.inv, w->inv, sizeof(a.inv));
+  a.d = w->d;
+  a.d_inv32 = w->d_inv32;
+  a.p_inv_d = w->p_inv_d;
+  a.d_recip = w->d_recip;
+  std::memcpy(a.w, w->w, sizeof(a.w));
+  const int inv = w->has_inv;
+  if (inv < 0 || inv > 2 || (inv == 2 && (w->d < 3 || w->d >= 65536 || !(w->d & 1))))
+    return set_error(DN_ERR_ARG, "%s: malformed divisor", name);
+  return DN_OK;
+}
+
+// Pinned staging for a table that an entry point uploads WITHOUT synchronising
+// its stream (dn_m521_reconstruct_many).  A buffer carries an event; whoever
+// used it records the event on its stream behind the copy before handing the
+// buffer back, and it is handed out again only once that event has completed
+// (or to nobody: a busy buffer is skipped and a new one made).  So a buffer is
+// never rewritten while a copy may still read it, whichever thread or stream
+// asks next: buffers are not tied to a stream, and one is in a single call's
+// hands between take() and give().  The pool is leaked on purpose (the HIP
+// runtime may be torn down before static destructors run).
+struct StageBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  hipEvent_t ev = nullptr;
+  int dev = -1;
+};
+
+struct StagePool {
+  std::mutex m;
+  std::vector<StageBuf> bufs;  // not in a call's hands (their events may be pending)
+};
+
+static StagePool& stage_pool() {
+  static StagePool* pool = new StagePool;
+  return *pool;
+}
+
+// A buffer of at least `need` bytes whose last copy has completed; .p null on failure.
+static StageBuf stage_take(size_t need) {
+  StageBuf b;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return b;
+  {
+    StagePool& pool = stage_pool();
+    std::lock_guard<std::mutex> g(pool.m);
+    for (size_t i = 0; i < pool.bufs.size(); ++i) {
+      if (pool.bufs[i].dev != dev || hipEventQuery(pool.bufs[i].ev) != hipSuccess) continue;
+      b = pool.bufs[i];
+      pool.bufs.erase(pool.bufs.begin() + static_cast<std::ptrdiff_t>(i));
+      break;
+    }
+    (void)hipGetLastError();  // (hipErrorNotReady of a pending event is no error of this call)
+  }
+  if (!b.ev) {
+    if (hipEventCreateWithFlags(&b.ev, hipEventDisableTiming) != hipSuccess) return StageBuf{};
+    b.dev = dev;
+  }
+  if (b.bytes < need) {  // idle and too small: replaced
+    if (b.p) (void)hipHostFree(b.p);
+    b.bytes = need < 4096 ? 4096 : need;
+    if (hipHostMalloc(&b.p, b.bytes, hipHostMallocDefault) != hipSuccess) {
+      (void)hipEventDestroy(b.ev);
+      return StageBuf{};
+    }
+  }
+  return b;
+}
+
+// Back to the pool; `s`: the stream whose queued copies read the buffer (null
+// pointer argument: none were queued).
+static void stage_give(StageBuf b, const hipStream_t* s) {
+  if (s && hipEventRecord(b.ev, *s) != hipSuccess) {
+    (void)hipStreamSynchronize(*s);  // no marker behind the copy: wait for it instead
+  }
+  StagePool& pool = stage_pool();
+  std::lock_guard<std::mutex> g(pool.m);
+  pool.bufs.push_back(b);
+}
+
 }  // namespace dn
 
 using namespace dn;
@@ -914,18 +1145,31 @@ extern "C" int dn_m521_split_fe(const void* secrets_fe, const void* coeffs, void
   return split_common(a, threshold, n_shares, stream, true, "dn_m521_split_fe");
 }
 
+// launch_recon_k / launch_recon_many_k for the descriptor's (a_limbs, has_inv)
+#define DN_RECON_DISPATCH(LAUNCH, W, ...)                       \
+  switch ((W)->a_limbs * 4 + (W)->has_inv) {                    \
+    case 1 * 4 + 0: LAUNCH<1, 0>(__VA_ARGS__); break;           \
+    case 1 * 4 + 1: LAUNCH<1, 1>(__VA_ARGS__); break;           \
+    case 1 * 4 + 2: LAUNCH<1, 2>(__VA_ARGS__); break;           \
+    case 2 * 4 + 0: LAUNCH<2, 0>(__VA_ARGS__); break;           \
+    case 2 * 4 + 1: LAUNCH<2, 1>(__VA_ARGS__); break;           \
+    case 2 * 4 + 2: LAUNCH<2, 2>(__VA_ARGS__); break;           \
+    case 17 * 4 + 0: LAUNCH<17, 0>(__VA_ARGS__); break;         \
+    case 17 * 4 + 1: LAUNCH<17, 1>(__VA_ARGS__); break;         \
+    default: LAUNCH<17, 2>(__VA_ARGS__); break;                 \
+  }
+
 extern "C" int dn_m521_reconstruct(const void* const* share_vecs, const dn_m521_lagrange_t* w, void* out_fe,
                                    int64_t* out_u64, uint32_t* overflow_count, uint64_t n_elem, void* stream) {
-  if (!w || !share_vecs) return set_error(DN_ERR_ARG, "dn_m521_reconstruct: null pointer");
-  if (w->k < 1 || w->k > DN_MAX_RESOLVE)
-    return set_error(DN_ERR_UNSUPPORTED, "dn_m521_reconstruct: k=%d outside 1..%d", w->k, DN_MAX_RESOLVE);
-  if (!(w->a_limbs == 1 || w->a_limbs == 2 || w->a_limbs == 17) || w->shift < 0 || w->shift > 31)
-    return set_error(DN_ERR_ARG, "dn_m521_reconstruct: malformed weights");
+  const char* name = "dn_m521_reconstruct";
+  if (!w || !share_vecs) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+  int rc = recon_check_weights(w, name);
+  if (rc != DN_OK) return rc;
   if (n_elem == 0) return DN_OK;
-  if (!out_fe && !out_u64) return set_error(DN_ERR_ARG, "dn_m521_reconstruct: no output");
+  if (!out_fe && !out_u64) return set_error(DN_ERR_ARG, "%s: no output", name);
   ReconArgs a{};
   for (int i = 0; i < w->k; ++i) {
-    if (!share_vecs[i]) return set_error(DN_ERR_ARG, "dn_m521_reconstruct: null share vector %d", i);
+    if (!share_vecs[i]) return set_error(DN_ERR_ARG, "%s: null share vector %d", name, i);
     a.shares[i] = static_cast<const uint8_t*>(share_vecs[i]);
   }
   a.out_fe = static_cast<uint8_t*>(out_fe);
@@ -933,34 +1177,90 @@ extern "C" int dn_m521_reconstruct(const void* const* share_vecs, const dn_m521_
   a.overflow = overflow_count;
   a.n_elem = n_elem;
   a.ntiles = (n_elem + kTile - 1) / kTile;
-  a.k = w->k;
-  a.neg = w->neg;
-  a.shift = static_cast<uint32_t>(w->shift);
-  std::memcpy(a.a, w->a, sizeof(a.a));
-  std::memcpy(a.inv, w->inv, sizeof(a.inv));
   const dim3 g(grid_for(a.ntiles));
   a.tile_map = tile_map_for(static_cast<int>(g.x));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  a.d = w->d;
-  a.d_inv32 = w->d_inv32;
-  a.p_inv_d = w->p_inv_d;
-  a.d_recip = w->d_recip;
-  std::memcpy(a.w, w->w, sizeof(a.w));
-  const int inv = w->has_inv;
-  if (inv < 0 || inv > 2 || (inv == 2 && (w->d < 3 || w->d >= 65536 || !(w->d & 1))))
-    return set_error(DN_ERR_ARG, "dn_m521_reconstruct: malformed divisor");
-#define DN_RECON(AL, IV) launch_recon_k<AL, IV>(w->k, g, s, a)
-  switch (w->a_limbs * 4 + inv) {
-    case 1 * 4 + 0: DN_RECON(1, 0); break;
-    case 1 * 4 + 1: DN_RECON(1, 1); break;
-    case 1 * 4 + 2: DN_RECON(1, 2); break;
-    case 2 * 4 + 0: DN_RECON(2, 0); break;
-    case 2 * 4 + 1: DN_RECON(2, 1); break;
-    case 2 * 4 + 2: DN_RECON(2, 2); break;
-    case 17 * 4 + 0: DN_RECON(17, 0); break;
-    case 17 * 4 + 1: DN_RECON(17, 1); break;
-    default: DN_RECON(17, 2); break;
-  }
-#undef DN_RECON
-  return check_launch("dn_m521_reconstruct");
+  rc = recon_set_weights(a, w, name);
+  if (rc != DN_OK) return rc;
+  DN_RECON_DISPATCH(launch_recon_k, w, w->k, g, s, a)
+  return check_launch(name);
 }
+
+// dn_m521_reconstruct over a list of vectors in one launch
+// (reconstruct_many_kernel).  scratch: the table's nseg + 1 entries, then the
+// nseg * k row addresses.
+extern "C" uint64_t dn_m521_reconstruct_many_scratch_bytes(uint64_t n_segments, int k) {
+  const uint64_t kk = k > 0 ? static_cast<uint64_t>(k) : 0u;
+  return (n_segments + 1) * sizeof(ReconSegEnt) + n_segments * kk * sizeof(uint64_t);
+}
+
+extern "C" int dn_m521_reconstruct_many(const uint64_t* n_elem, const void* const* share_vecs, void* const* out_fe,
+                                        int64_t* const* out_u64, uint32_t* overflow_counts, uint64_t n_segments,
+                                        const dn_m521_lagrange_t* w, void* scratch, uint64_t scratch_bytes,
+                                        void* stream) {
+  const char* name = "dn_m521_reconstruct_many";
+  if (!w) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+  int rc = recon_check_weights(w, name);
+  if (rc != DN_OK) return rc;
+  if (n_segments > kMaxSegments)
+    return set_error(DN_ERR_ARG, "%s: %llu segments (at most %llu)", name, static_cast<unsigned long long>(n_segments),
+                     static_cast<unsigned long long>(kMaxSegments));
+  if (n_segments && !n_elem) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+  const uint64_t k = static_cast<uint64_t>(w->k);
+  uint64_t nseg = 0, ntiles = 0;
+  for (uint64_t j = 0; j < n_segments; ++j) {
+    if (!n_elem[j]) continue;  // an empty vector: none of its pointers is read
+    if (n_elem[j] > (1ull << 40)) return set_error(DN_ERR_ARG, "%s: vector %llu too long", name,
+                                                   static_cast<unsigned long long>(j));
+    ntiles += (n_elem[j] + kTile - 1) / kTile;
+    ++nseg;
+  }
+  if (!nseg) return DN_OK;
+  if (ntiles >= (1ull << 32)) return set_error(DN_ERR_ARG, "%s: more than 2^32 tiles", name);
+  if (!share_vecs) return set_error(DN_ERR_ARG, "%s: null pointer", name);
+  if (!out_fe && !out_u64) return set_error(DN_ERR_ARG, "%s: no output", name);
+  for (uint64_t j = 0; j < n_segments; ++j) {
+    if (!n_elem[j]) continue;
+    if ((out_fe && !out_fe[j]) || (out_u64 && !out_u64[j]))
+      return set_error(DN_ERR_ARG, "%s: null output of vector %llu", name, static_cast<unsigned long long>(j));
+    for (uint64_t i = 0; i < k; ++i)
+      if (!share_vecs[j * k + i])
+        return set_error(DN_ERR_ARG, "%s: null share vector %d", name, static_cast<int>(i));
+  }
+  ReconManyArgs a{};
+  rc = recon_set_weights(a.r, w, name);
+  if (rc != DN_OK) return rc;
+  const uint64_t ent_bytes = (nseg + 1) * sizeof(ReconSegEnt), tab_bytes = ent_bytes + nseg * k * sizeof(uint64_t);
+  if (!scratch || scratch_bytes < dn_m521_reconstruct_many_scratch_bytes(n_segments, w->k))
+    return set_error(DN_ERR_ARG, "%s: scratch too small", name);
+  StageBuf stage = stage_take(tab_bytes);
+  if (!stage.p) return set_error(DN_ERR_HIP, "%s: pinned staging buffer", name);
+  ReconSegEnt* ent = static_cast<ReconSegEnt*>(stage.p);
+  uint64_t* rows = reinterpret_cast<uint64_t*>(static_cast<uint8_t*>(stage.p) + ent_bytes);
+  uint64_t s = 0, t = 0;
+  for (uint64_t j = 0; j < n_segments; ++j) {
+    if (!n_elem[j]) continue;
+    ent[s] = ReconSegEnt{static_cast<uint32_t>(t), 0u, n_elem[j], out_fe ? static_cast<uint8_t*>(out_fe[j]) : nullptr,
+                         out_u64 ? out_u64[j] : nullptr, overflow_counts ? overflow_counts + j : nullptr};
+    for (uint64_t i = 0; i < k; ++i) rows[s * k + i] = reinterpret_cast<uint64_t>(share_vecs[j * k + i]);
+    t += (n_elem[j] + kTile - 1) / kTile;
+    ++s;
+  }
+  ent[s] = ReconSegEnt{static_cast<uint32_t>(ntiles), 0u, 0u, nullptr, nullptr, nullptr};
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemcpyAsync(scratch, stage.p, tab_bytes, hipMemcpyHostToDevice, st) != hipSuccess) {
+    stage_give(stage, nullptr);
+    return set_error(DN_ERR_HIP, "%s: table upload", name);
+  }
+  stage_give(stage, &st);
+  a.segs = static_cast<const ReconSegEnt*>(scratch);
+  a.rows = reinterpret_cast<const uint8_t* const*>(static_cast<const uint8_t*>(scratch) + ent_bytes);
+  a.nseg = static_cast<uint32_t>(nseg);
+  a.r.ntiles = ntiles;
+  const dim3 g(grid_for(ntiles));
+  a.r.tile_map = tile_map_for(static_cast<int>(g.x));
+  DN_RECON_DISPATCH(launch_recon_many_k, w, w->k, g, st, a)
+  return check_launch(name);
+}
+#undef DN_RECON_DISPATCH
+

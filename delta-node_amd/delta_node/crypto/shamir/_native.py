@@ -50,6 +50,7 @@ EXPORTS = (
     "dn_block_record", "dn_block_ready", "dn_block_acquire", "dn_block_retired_bytes",
     "dn_mt19937_rt_rows_embedded", "dn_mt19937_spec_stats", "dn_mt19937_jump_poly",
     "dn_mt19937_split_many_scratch_bytes", "dn_mt19937_split_many_supported", "dn_mt19937_split_many_device",
+    "dn_m521_reconstruct_many_scratch_bytes", "dn_m521_reconstruct_many",
 )
 
 
@@ -189,6 +190,12 @@ def _load(path: str) -> ctypes.CDLL:
         L.dn_mt19937_split_many_supported.argtypes = [u64, i32, i32, u64]
         L.dn_mt19937_split_many_device.restype = i32
         L.dn_mt19937_split_many_device.argtypes = [vp, vp, vp, ctypes.POINTER(Segment), u64, i32, i32, vp, u64, vp]
+    if hasattr(L, "dn_m521_reconstruct_many"):
+        L.dn_m521_reconstruct_many_scratch_bytes.restype = u64
+        L.dn_m521_reconstruct_many_scratch_bytes.argtypes = [u64, i32]
+        L.dn_m521_reconstruct_many.restype = i32
+        L.dn_m521_reconstruct_many.argtypes = [ctypes.POINTER(u64), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                               ctypes.POINTER(vp), vp, u64, ctypes.POINTER(Lagrange), vp, u64, vp]
     L.dn_block_retired_bytes.restype = i32
     L.dn_block_retired_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.dn_block_probe_rows.restype = i32
@@ -329,6 +336,32 @@ def reconstruct(share_vecs: Sequence, w: Lagrange, out_fe=None, out_u64=None, ov
     ptrs = (ctypes.c_void_p * k)(*[v.data_ptr() for v in share_vecs])
     check(lib().dn_m521_reconstruct(ptrs, ctypes.byref(w), _ptr(out_fe), _ptr(out_u64), _ptr(overflow), n,
                                     stream_ptr()))
+
+
+def reconstruct_many(ns: Sequence[int], row_ptrs: Sequence[int], w: Lagrange, device, out_fe_ptrs=None,
+                     out_u64_ptrs=None, overflow=None) -> None:
+    """`reconstruct` over a list of vectors in one launch
+    (dn_m521_reconstruct_many): ns[j] elements of vector j, row_ptrs the flat
+    list of len(ns) * w.k device addresses (vector-major, rows in the weights'
+    order), out_*_ptrs one device address per vector, overflow a device int32 /
+    uint32 tensor [len(ns)] or None (the caller has validated its tensors: a
+    model's hundred tensors are not walked twice).  Does not synchronise: the
+    table scratch is a fresh stream-ordered allocation per call."""
+    import torch
+
+    m = len(ns)
+    if len(row_ptrs) != m * w.k:
+        raise ValueError("reconstruct_many: one row address per vector and weight")
+    L = lib()
+    if not hasattr(L, "dn_m521_reconstruct_many"):
+        raise RuntimeError(f"{lib_path()} lacks dn_m521_reconstruct_many: rebuild the native library")
+    sb = int(L.dn_m521_reconstruct_many_scratch_bytes(m, w.k))
+    scratch = torch.empty(sb, dtype=torch.uint8, device=device)
+    arr = ctypes.c_void_p * m
+    check(L.dn_m521_reconstruct_many((ctypes.c_uint64 * m)(*ns), (ctypes.c_void_p * len(row_ptrs))(*row_ptrs),
+                                     arr(*out_fe_ptrs) if out_fe_ptrs is not None else None,
+                                     arr(*out_u64_ptrs) if out_u64_ptrs is not None else None, _ptr(overflow), m,
+                                     ctypes.byref(w), scratch.data_ptr(), sb, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

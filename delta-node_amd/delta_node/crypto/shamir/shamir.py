@@ -483,3 +483,92 @@ class SecretShare(object):
         else:
             raise ValueError('resolve_shares_vec: out must be "int64" or "field"')
         return (res, over) if return_overflow else res
+
+    def resolve_shares_vec_many(self, shares, xs: Sequence[int], ns: Sequence[int], *, out: str = "int64",
+                                outs=None, return_overflow: bool = False):
+        """`[self.resolve_shares_vec(shares[j], xs, ns[j], out=out) for j ...]`
+        in one launch — the receiving side of `make_shares_vec_many`.
+
+        shares  per tensor j: a uint8 device tensor [k, vec_bytes(ns[j])] whose
+                rows are in `xs` order, or a sequence of k contiguous vectors
+                [vec_bytes(ns[j])] (`[blk[x - 1] for x in xs]` on a block of
+                make_shares_vec_many)
+        xs      the k abscissas, shared by all tensors
+        ns      elements per tensor
+        out     as resolve_shares_vec
+        outs    optional caller outputs, outs[j] contiguous int64 [ns[j]]
+                (out="int64") or uint8 [vec_bytes(ns[j])] (out="field");
+                default: consecutive views of ONE allocation
+        return_overflow  also return one int32 device tensor [len(ns)]: per
+                tensor, its elements >= 2^64
+        Same checks as `resolve_shares_vec`, before any device work.  The
+        Lagrange weights are computed once.  Nothing here synchronises.  Where
+        the one-launch form does not apply (k > 16, an abscissa outside 64
+        bits: the grouped full-width path) the per-tensor loop runs into the
+        same outputs."""
+        self._require_m521()
+        import torch
+
+        shares, ns = list(shares), [int(n) for n in ns]
+        xs = [int(x) for x in xs]
+        k = len(xs)
+        if len(shares) != len(ns):
+            raise ValueError(f"resolve_shares_vec_many: {len(shares)} share entries for {len(ns)} tensors")
+        for sh in shares:
+            if (sh.shape[0] if isinstance(sh, torch.Tensor) and sh.dim() == 2 else len(sh)) != k:
+                raise ValueError("resolve_shares_vec: one abscissa per share vector")
+        if k == 0:
+            raise ValueError("not enough values to unpack (expected 2, got 0)")
+        if k < self.threshold:
+            raise ValueError("need at least {} shares".format(self.threshold))
+        if k != len(set(xs)):
+            raise ValueError("shares must be distinct")
+        if k == 1:
+            raise TypeError("reduce() of empty iterable with no initial value")
+        if out not in ("int64", "field"):
+            raise ValueError('resolve_shares_vec_many: out must be "int64" or "field"')
+        dev = _device()
+        vbs = [field.vec_bytes(n) for n in ns]
+        u8 = torch.uint8
+        rows: List[int] = []  # k row addresses per tensor
+        for sh, vb in zip(shares, vbs):
+            if isinstance(sh, torch.Tensor) and sh.dim() == 2:
+                if sh.dtype != u8 or sh.shape[1] != vb or sh.device != dev or not sh.is_contiguous():
+                    raise ValueError(f"resolve_shares_vec_many: share rows must be contiguous uint8 [{k}, {vb}] on {dev}")
+                p = sh.data_ptr()
+                rows.extend(range(p, p + k * vb, vb) if vb else [p] * k)
+                continue
+            for v in sh:
+                if v.dtype != u8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
+                    raise ValueError(f"resolve_shares_vec_many: share vectors must be contiguous uint8 [{vb}] on {dev}")
+                rows.append(v.data_ptr())
+        as_int = out == "int64"
+        sizes = ns if as_int else vbs
+        if outs is None:
+            flat = torch.empty(sum(sizes), dtype=torch.int64 if as_int else u8, device=dev)
+            outs = list(torch.split(flat, sizes)) if sizes else []
+            optrs, off, step = [], flat.data_ptr(), 8 if as_int else 1
+            for sz in sizes:
+                optrs.append(off)
+                off += step * sz
+        else:
+            outs = list(outs)
+            if len(outs) != len(ns):
+                raise ValueError(f"resolve_shares_vec_many: {len(outs)} outs for {len(ns)} tensors")
+            want = torch.int64 if as_int else u8
+            for o, sz in zip(outs, sizes):
+                if o.dtype != want or tuple(o.shape) != (sz,) or not o.is_contiguous() or o.device != dev:
+                    raise ValueError(f"resolve_shares_vec_many: out must be contiguous {out} [{sz}] on {dev}")
+            optrs = [o.data_ptr() for o in outs]
+        over = torch.zeros(len(ns), dtype=torch.int32, device=dev) if return_overflow else None
+        if k <= _native.MAX_RESOLVE and all(0 <= x < (1 << 64) for x in xs):
+            if ns:
+                w = _native.lagrange(xs, self.threshold)
+                _native.reconstruct_many(ns, rows, w, dev, out_fe_ptrs=None if as_int else optrs,
+                                         out_u64_ptrs=optrs if as_int else None, overflow=over)
+        else:  # the calls this one stands for, into the same outputs
+            for j, (sh, n, o) in enumerate(zip(shares, ns, outs)):
+                vecs = list(sh.unbind(0)) if isinstance(sh, torch.Tensor) and sh.dim() == 2 else list(sh)
+                _resolve_vectors(vecs, xs, n, self.threshold, out_fe=None if as_int else o,
+                                 out_u64=o if as_int else None, overflow=None if over is None else over[j:j + 1])
+        return (outs, over) if return_overflow else outs

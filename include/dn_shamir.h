@@ -164,6 +164,40 @@ int dn_m521_reconstruct(const void* const* share_vecs, const dn_m521_lagrange_t*
                         uint64_t n_elem, void* stream);
 
 /*
+ * dn_m521_reconstruct over a LIST of vectors in one launch — the receiving
+ * side of dn_mt19937_split_many_device: every vector has its own tiled share
+ * rows and outputs, the weights *w are shared by all of them.
+ *   n_elem          HOST array [n_segments]: elements of vector j
+ *   share_vecs      HOST array [n_segments * k] of DEVICE pointers: entry
+ *                   j * k + i is share row i (abscissa i of *w) of vector j, a
+ *                   tiled vector of n_elem[j] elements
+ *   out_fe          HOST array [n_segments] of device tiled vectors, or NULL
+ *   out_u64         HOST array [n_segments] of device int64[n_elem[j]], or NULL
+ *   overflow_counts DEVICE uint32[n_segments], or NULL: counter j is
+ *                   incremented once per element of vector j that is >= 2^64
+ *   scratch         device memory of dn_m521_reconstruct_many_scratch_bytes(
+ *                   n_segments, k) bytes; the kernel reads it, so it must stay
+ *                   untouched until the work queued on `stream` has run
+ * A vector with n_elem[j] == 0 is skipped and none of its pointers is read.
+ * At most 65536 vectors.  Validation and codes as dn_m521_reconstruct.  The
+ * results equal dn_m521_reconstruct on vector 0, 1, ... in turn.
+ *
+ * Like dn_m521_reconstruct this call does NOT synchronise `stream`.  The
+ * table (tile ranges, outputs, row addresses) is written into a pinned host
+ * buffer and copied to `scratch` by hipMemcpyAsync on `stream`; the buffer
+ * carries an event, recorded on `stream` behind the copy, and is handed to a
+ * later call — of any thread, on any stream — only once that event has
+ * completed; while it has not, later calls take or make another buffer.  This
+ * relies on stream order alone (the copy precedes the event and the kernel)
+ * and holds no buffer per device or stream.  Because of the event query the
+ * call cannot be captured into a graph.
+ */
+uint64_t dn_m521_reconstruct_many_scratch_bytes(uint64_t n_segments, int k);
+int dn_m521_reconstruct_many(const uint64_t* n_elem, const void* const* share_vecs, void* const* out_fe,
+                             int64_t* const* out_u64, uint32_t* overflow_counts, uint64_t n_segments,
+                             const dn_m521_lagrange_t* w, void* scratch, uint64_t scratch_bytes, void* stream);
+
+/*
  * Host.  Draw the reference's coefficients with CPython's MT19937 semantics:
  * for each element e (in order) and j = 1..t-1, c = randint(1, p-1) =
  * 1 + getrandbits(521) rejected while >= p-1 (17 MT words, little-endian, last
