@@ -50,7 +50,7 @@ EXPORTS = (
     "dn_block_record", "dn_block_ready", "dn_block_acquire", "dn_block_retired_bytes",
     "dn_mt19937_rt_rows_embedded", "dn_mt19937_spec_stats", "dn_mt19937_jump_poly",
     "dn_mt19937_split_many_scratch_bytes", "dn_mt19937_split_many_supported", "dn_mt19937_split_many_device",
-    "dn_m521_reconstruct_many_scratch_bytes", "dn_m521_reconstruct_many",
+    "dn_m521_reconstruct_many_scratch_bytes", "dn_m521_reconstruct_many", "dn_m521_sum_vecs",
 )
 
 
@@ -196,6 +196,9 @@ def _load(path: str) -> ctypes.CDLL:
         L.dn_m521_reconstruct_many.restype = i32
         L.dn_m521_reconstruct_many.argtypes = [ctypes.POINTER(u64), ctypes.POINTER(vp), ctypes.POINTER(vp),
                                                ctypes.POINTER(vp), vp, u64, ctypes.POINTER(Lagrange), vp, u64, vp]
+    if hasattr(L, "dn_m521_sum_vecs"):
+        L.dn_m521_sum_vecs.restype = i32
+        L.dn_m521_sum_vecs.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p, u64, vp, u64, vp]
     L.dn_block_retired_bytes.restype = i32
     L.dn_block_retired_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.dn_block_probe_rows.restype = i32
@@ -362,6 +365,21 @@ def reconstruct_many(ns: Sequence[int], row_ptrs: Sequence[int], w: Lagrange, de
                                      arr(*out_fe_ptrs) if out_fe_ptrs is not None else None,
                                      arr(*out_u64_ptrs) if out_u64_ptrs is not None else None, _ptr(overflow), m,
                                      ctypes.byref(w), scratch.data_ptr(), sb, stream_ptr()))
+
+
+def sum_vecs(ptrs: Sequence[int], negate: Optional[Sequence[bool]], out_ptr: int, n_tiles: int) -> None:
+    """out = sum_i +-vecs_i mod p over n_tiles tiles (dn_m521_sum_vecs): ptrs
+    the m device addresses, negate m flags (true: subtract) or None, out_ptr
+    the output's address (it may be one of ptrs).  Any m: the entry point
+    chains launches of DN_M521_SUM_GROUP inputs.  Does not synchronise."""
+    L = lib()
+    if not hasattr(L, "dn_m521_sum_vecs"):
+        raise RuntimeError(f"{lib_path()} lacks dn_m521_sum_vecs: rebuild the native library")
+    m = len(ptrs)
+    neg = None if negate is None else bytes(1 if f else 0 for f in negate)
+    if neg is not None and len(neg) != m:
+        raise ValueError("sum_vecs: one negate flag per input")
+    check(L.dn_m521_sum_vecs((ctypes.c_void_p * max(m, 1))(*ptrs), neg, m, out_ptr, n_tiles, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

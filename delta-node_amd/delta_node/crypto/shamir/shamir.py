@@ -32,6 +32,7 @@ path (csrc/host_shamir.cpp) for any prime, like the reference's
 """
 from __future__ import annotations
 
+import numbers
 import random
 from functools import reduce
 from typing import List, Optional, Sequence, Tuple, Union
@@ -572,3 +573,65 @@ class SecretShare(object):
                 _resolve_vectors(vecs, xs, n, self.threshold, out_fe=None if as_int else o,
                                  out_u64=o if as_int else None, overflow=None if over is None else over[j:j + 1])
         return (outs, over) if return_overflow else outs
+
+    def sum_shares_vec(self, blocks, *, signs=None, out=None):
+        """Sum members' share vectors mod p, element-wise, in one launch —
+        the party-side step of share-domain aggregation.
+
+        Shamir is additively homomorphic: party x that receives share x of
+        every member's tensor and adds the m vectors holds share x of the
+        tensors' sum, so `resolve_shares_vec` on any t parties' sums gives the
+        sum of the members' tensors and nobody sees a single member's.
+
+        blocks  sequence of m uint8 device tensors of one shape, contiguous,
+                numel a multiple of field.TILE_BYTES: vectors [vec_bytes(n)],
+                blocks [S, vec_bytes(n)] or the flat buffer behind a
+                make_shares_vec_many result alike (the sum is tile-local; all
+                256 lanes of every tile are summed: zero padding in, zero
+                padding out).  One tensor [m, ...] is unbound along dim 0
+        signs   optional m values, each +1 or -1 (-1: subtract that member —
+                one dropped after the sum was taken)
+        out     optional tensor of the blocks' shape, dtype and device; it may
+                be one of the blocks (accumulate in place).  Default:
+                torch.empty_like(blocks[0])
+        Returns the output tensor: canonical residues.  Runs on the current
+        stream and does not synchronise; uses neither self.threshold nor
+        self.random.  Any m: beyond DN_M521_SUM_GROUP inputs the native entry
+        point chains launches that accumulate into `out`."""
+        self._require_m521()
+        import torch
+
+        blocks = list(blocks.unbind(0)) if isinstance(blocks, torch.Tensor) and blocks.dim() >= 1 else list(blocks)
+        if not blocks:
+            raise ValueError("sum_shares_vec: no blocks")
+        first = blocks[0]
+        for b in blocks:
+            if not isinstance(b, torch.Tensor) or b.dtype != torch.uint8:
+                raise ValueError("sum_shares_vec: blocks must be uint8 tensors")
+            if b.shape != first.shape or b.device != first.device:
+                raise ValueError(f"sum_shares_vec: blocks must share one shape and device, got {tuple(b.shape)} on "
+                                 f"{b.device} next to {tuple(first.shape)} on {first.device}")
+            if not b.is_contiguous():
+                raise ValueError("sum_shares_vec: blocks must be contiguous")
+        if first.numel() % field.TILE_BYTES:
+            raise ValueError(f"sum_shares_vec: blocks must be whole {field.TILE_BYTES}-byte tiles, "
+                             f"got {first.numel()} bytes")
+        negate = None
+        if signs is not None:
+            signs = list(signs)
+            if len(signs) != len(blocks):
+                raise ValueError(f"sum_shares_vec: {len(signs)} signs for {len(blocks)} blocks")
+            if any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s not in (1, -1) for s in signs):
+                raise ValueError("sum_shares_vec: signs must be +1 or -1")
+            negate = [s < 0 for s in signs]
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8
+                                or out.shape != first.shape or out.device != first.device
+                                or not out.is_contiguous()):
+            raise ValueError(f"sum_shares_vec: out must be contiguous uint8 {tuple(first.shape)} on {first.device}")
+        dev = _device()
+        if first.device != dev:
+            raise ValueError(f"sum_shares_vec: blocks must be on {dev}")
+        if out is None:
+            out = torch.empty_like(first)
+        _native.sum_vecs([b.data_ptr() for b in blocks], negate, out.data_ptr(), first.numel() // field.TILE_BYTES)
+        return out

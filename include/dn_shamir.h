@@ -198,6 +198,37 @@ int dn_m521_reconstruct_many(const uint64_t* n_elem, const void* const* share_ve
                              const dn_m521_lagrange_t* w, void* scratch, uint64_t scratch_bytes, void* stream);
 
 /*
+ * Sum of share vectors: out_e = (sum_i +-y_{i,e}) mod p, canonical, for every
+ * lane of every tile — the share-domain counterpart of dn_i64_sum.  Shamir is
+ * additively homomorphic: a party that adds share x of every member's tensor
+ * holds share x of the tensors' sum (no reference counterpart: the reference
+ * sums masked results, coord/horizontal/agg.py:227-251, never shares).
+ *   vecs     HOST array of m DEVICE pointers, each n_tiles tiles (n_tiles *
+ *            DN_M521_TILE_BYTES bytes) of tiled field elements: a vector, a
+ *            block of vectors or the flat buffer behind a list of blocks — the
+ *            sum is tile-local and needs neither n_elem nor a row structure.
+ *            Values < 2^521 (bits 9..15 of the top plane are ignored, p itself
+ *            is a legal input); all 256 lanes of every tile are summed, padding
+ *            lanes included (zero padding in, zero padding out)
+ *   negate   HOST array of m flags (non-zero: input i is subtracted), or NULL
+ *   out      DEVICE, n_tiles tiles
+ * Nothing outside those byte ranges is read or written.  `out` may equal an
+ * input's address (accumulate in place as members' shares arrive) and an
+ * address may appear more than once; an input that overlaps `out` without
+ * being equal to it is DN_ERR_ARG.  One launch takes DN_M521_SUM_GROUP inputs
+ * (addresses and signs travel in the kernel arguments: no device table, no
+ * staging buffer); a longer list is chained — launch 1 writes `out`, each later
+ * launch adds the next GROUP - 1 inputs to it — with every input equal to
+ * `out` placed in launch 1, so no launch reads an `out` already overwritten
+ * (more such inputs than one launch holds: DN_ERR_ARG).  n_tiles == 0 returns
+ * DN_OK and touches no pointer; m == 0, a null pointer or n_tiles >= 2^32 is
+ * DN_ERR_ARG.  Does not synchronise `stream`; can be captured into a graph.
+ */
+#define DN_M521_SUM_GROUP 256
+int dn_m521_sum_vecs(const void* const* vecs, const uint8_t* negate, uint64_t m, void* out, uint64_t n_tiles,
+                     void* stream);
+
+/*
  * Host.  Draw the reference's coefficients with CPython's MT19937 semantics:
  * for each element e (in order) and j = 1..t-1, c = randint(1, p-1) =
  * 1 + getrandbits(521) rejected while >= p-1 (17 MT words, little-endian, last
