@@ -27,8 +27,9 @@ extern "C" {
 /* Row hashes of calc_data_commitment: data is device float64 [rows][cols]
  * (last column the label, converted at 10^21, the others at 10^8); rows are
  * padded with zero rows to a multiple of 128.  row_hashes: device
- * uint32 [round_up(rows,128)][8] = mimc7_hash_arr(row, 2) (mod q).  Values
- * with |v * 10^p| >= 2^253 are counted in *bad_count (device) — not handled. */
+ * uint32 [round_up(rows,128)][8] = mimc7_hash_arr(row, 2) (mod q).  Rows
+ * that hold at least one value with |v * 10^p| >= 2^253, NaN or +-inf are
+ * counted in *bad_count (device), once per row — not handled. */
 int dn_mimc7_data_rows(const double* data, uint64_t rows, int cols, uint32_t* row_hashes, uint32_t* bad_count,
                        void* stream);
 
@@ -38,7 +39,9 @@ int dn_mimc7_merkle_blocks(const uint32_t* leaves, uint64_t blocks, uint32_t* ro
 
 /* calc_weight_commitment's chain mimc7_hash_arr([_float2mpz(w, p) ...], 2) of
  * device float64 w[n]; out: device uint32[8].  One sequential chain (each
- * hash is keyed by the previous result): a single lane, latency-bound. */
+ * hash is keyed by the previous result): a single lane, latency-bound.
+ * precision 0..22.  *bad_count (device) is incremented once if any weight has
+ * |w * 10^p| >= 2^253, is NaN or +-inf — not handled. */
 int dn_mimc7_weight_chain(const double* w, uint64_t n, int precision, uint32_t* out, uint32_t* bad_count,
                           void* stream);
 
