@@ -498,7 +498,11 @@ extern "C" int dn_bounded_i64_accumulate(const dn_pcg64_t* gens, const int32_t* 
     else hipLaunchKernelGGL(bounded_acc_small_kernel<false>, dim3(blocks), dim3(kMaskBlock), 0, s, a);
   } else {
     const uint64_t tiles = (elem_end - elem_begin + kTileElems - 1) / kTileElems;
-    const dim3 grid(grid_for_tiles(tiles)), block(kMaskBlock);
+    int blocks = grid_for_tiles(tiles);
+    // tuning build: DN_MASK_BLOCKS caps the workgroups, so that every wave steps
+    // through many tiles at small n (the tile loop otherwise needs n > 2^27)
+    if (const char* bc = tune_env("DN_MASK_BLOCKS")) blocks = std::min(blocks, std::max(1, std::atoi(bc)));
+    const dim3 grid(blocks), block(kMaskBlock);
     const size_t lds = static_cast<size_t>(ngen) * kMaskBlock * sizeof(u128);
     if (a.mers_k) hipLaunchKernelGGL(bounded_acc_kernel<true>, grid, block, lds, s, a);
     else hipLaunchKernelGGL(bounded_acc_kernel<false>, grid, block, lds, s, a);

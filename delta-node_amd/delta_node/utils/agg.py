@@ -30,12 +30,19 @@ def sum_int64(tensors: Sequence, out=None):
     if any(t.numel() != n for t in ts):
         raise ValueError("sum_int64: shape mismatch")
     shape = tuple(torch.as_tensor(tensors[0]).shape)
+    # dn_i64_sum loads 16-byte pairs: a contiguous view that starts at an odd
+    # element of its buffer (a per-key slice of one flat receive buffer) is only
+    # 8-byte aligned and goes through an aligned copy; so does such an `out`
+    ts = [t if t.data_ptr() % 16 == 0 else t.clone() for t in ts]
     if out is None:
         out = torch.empty(n, dtype=torch.int64, device=dev)
-    mn.i64_sum(ts[:16], out, n)
+    acc = out if out.data_ptr() % 16 == 0 else torch.empty(n, dtype=torch.int64, device=dev)
+    mn.i64_sum(ts[:16], acc, n)
     rest = ts[16:]
-    for g in range(0, len(rest), 15):  # further inputs, 15 at a time on top of `out`
-        mn.i64_sum([out] + rest[g:g + 15], out, n)
+    for g in range(0, len(rest), 15):  # further inputs, 15 at a time on top of `acc`
+        mn.i64_sum([acc] + rest[g:g + 15], acc, n)
+    if acc is not out:
+        out.copy_(acc.reshape(out.shape))
     return out.reshape(shape)
 
 

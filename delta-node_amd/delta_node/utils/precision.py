@@ -40,6 +40,9 @@ def unfix_precision(arr, precision: int):
         out = torch.empty(x.numel(), dtype=torch.float64, device=dev)
         mn.unfix(x, out, x.numel(), int(precision))
     else:  # float inputs: the same IEEE float64 division, through torch on the device
-        out = t.to(dev).to(torch.float64).reshape(-1) / float(10 ** int(precision))
+        # (by a device tensor: torch turns a division by a host scalar into a
+        # multiplication by its reciprocal, which is not correctly rounded)
+        scale = torch.tensor(float(10 ** int(precision)), dtype=torch.float64, device=dev)
+        out = t.to(dev).to(torch.float64).reshape(-1) / scale
     out = out.reshape(shape)
     return out.cpu().numpy() if is_np else out
