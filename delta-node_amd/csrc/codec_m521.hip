@@ -423,6 +423,9 @@ extern "C" int dn_m521_encode_shares(const void* vec, uint64_t n_elem, uint64_t 
                                      uint64_t capacity, void* scratch, uint64_t scratch_bytes, void* stream) {
   if (n_elem == 0) return DN_OK;
   if (!vec || !offsets || !out || !scratch) return set_error(DN_ERR_ARG, "dn_m521_encode_shares: null pointer");
+  // the narrow path stores dwords at out + (an offset that is a multiple of 4)
+  if (reinterpret_cast<uintptr_t>(out) & 3u)
+    return set_error(DN_ERR_ARG, "dn_m521_encode_shares: out must be 4-byte aligned");
   if (capacity < dn_m521_encoded_capacity(n_elem, x))
     return set_error(DN_ERR_ARG, "dn_m521_encode_shares: capacity %llu < %llu", (unsigned long long)capacity,
                      (unsigned long long)dn_m521_encoded_capacity(n_elem, x));
@@ -461,6 +464,9 @@ extern "C" int dn_m521_decode_shares(const uint8_t* in, uint64_t in_bytes, const
                                      void* vec, uint64_t* xs, uint32_t* bad_count, void* stream) {
   if (n_elem == 0) return DN_OK;
   if (!in || !offsets || !vec || !bad_count) return set_error(DN_ERR_ARG, "dn_m521_decode_shares: null pointer");
+  // the narrow path loads dwords from in + (an offset that is a multiple of 4)
+  if (reinterpret_cast<uintptr_t>(in) & 3u)
+    return set_error(DN_ERR_ARG, "dn_m521_decode_shares: in must be 4-byte aligned");
   const uint64_t blocks = (n_elem + kCodecBlock - 1) / kCodecBlock;
   bool w16 = (reinterpret_cast<uintptr_t>(in) & 15u) == 0;
 #ifdef DN_TUNING

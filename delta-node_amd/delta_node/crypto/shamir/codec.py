@@ -63,7 +63,7 @@ def _out(t, numel: int, dtype, dev, what: str):
 
 def encode_share_vec(vec, n: int, x: int, *, trim: bool = True, out=None, offsets=None):
     """Share x of n elements (uint8 device tensor, tiled) -> (packed uint8, offsets int64[n+1]).
-    out / offsets: caller buffers (>= encoded_capacity(n, x) bytes, >= n + 1 entries), else allocated.
+    out / offsets: caller buffers (>= encoded_capacity(n, x) bytes, 4-byte aligned; >= n + 1 entries), else allocated.
     trim=True cuts `packed` to its length (one read-back of offsets[n])."""
     import torch
 
@@ -73,6 +73,8 @@ def encode_share_vec(vec, n: int, x: int, *, trim: bool = True, out=None, offset
     dev = vec.device
     cap = int(L.dn_m521_encoded_capacity(n, x))
     out = _out(out, max(cap, 1), torch.uint8, dev, "encode_share_vec out")
+    if out.data_ptr() & 3:
+        raise ValueError("encode_share_vec out: the buffer must be 4-byte aligned (the encoder stores dwords)")
     # every entry is written by the encoder (offsets[n] by the last element)
     if n:
         offsets = _out(offsets, n + 1, torch.int64, dev, "encode_share_vec offsets")[: n + 1]
@@ -100,6 +102,7 @@ def decode_share_vec(packed, offsets, n: int, *, out=None, xs=None, bad=None):
     """(packed, offsets[n+1]) -> (tiled uint8 vector of y mod p, uint64 xs as int64 tensor).
 
     out / xs: caller buffers (>= vec_bytes(n) bytes, >= n entries), else allocated.
+    A `packed` view that is not 4-byte aligned is copied once (the kernels load dwords).
     bad=None: the call checks for records it cannot represent (x > 8 bytes,
     y > 68 bytes) with one read-back and raises ValueError.  bad=<int32 device
     tensor>: the count of such records is ADDED to it on the device and the
@@ -109,6 +112,8 @@ def decode_share_vec(packed, offsets, n: int, *, out=None, xs=None, bad=None):
 
     L = _lib()
     dev = packed.device
+    if packed.data_ptr() & 3:  # the decoder loads dwords: one aligned device copy of a misaligned view
+        packed = packed.clone()
     vec = _out(out, field.vec_bytes(n), torch.uint8, dev, "decode_share_vec out")
     xs = _out(xs, max(n, 1), torch.int64, dev, "decode_share_vec xs")
     checked = bad is None

@@ -452,6 +452,8 @@ int dn_mt19937_jump_poly(uint64_t words, uint64_t* out);
  * is exactly the reference's bytes for share (x, y_e):
  *     [len(xb)][xb][yb],  xb / yb minimal big-endian (0 -> empty)
  * and records are back to back: record e = out[offsets[e] : offsets[e+1]].
+ * `out` (encode) and `in` (decode) must be 4-byte aligned, else DN_ERR_ARG and
+ * nothing is launched; 16-byte aligned buffers take the wide (16-byte) path.
  */
 /* Device scratch bytes dn_m521_encode_shares needs for n elements. */
 uint64_t dn_m521_codec_scratch_bytes(uint64_t n_elem);

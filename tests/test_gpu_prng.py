@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import wire_edges as we
 from delta_node.crypto import shamir
 from delta_node.crypto.shamir import _native, field
 from golden.fixtures import P, secrets_int64
@@ -101,3 +102,61 @@ def test_split_prng_argument_errors():
         _native.split_prng(sec, KEY, 0, 20, 0, sh, 256, 6, 5)  # t > n
     with pytest.raises(ValueError):
         _native.split_prng(sec, KEY[:16], 0, 20, 0, sh, 256, 3, 5)
+
+
+# ---- the 64-bit block counter (tests/wire_edges.py) -------------------------------
+# The coefficient index i = g (t - 1) + (j - 1) is ChaCha's block counter; a
+# sharded draw starts at a large elem_offset, and with it word 13 of the low
+# blocks stops being 0.  A 32-bit truncation anywhere on that path passes every
+# test above (elem_offset <= 256 256).
+COUNTER_N = 768
+COUNTER_CASES = [(t, we.prng_offset_below_2_32(t)) for t in (2, 3, 4, 8)] + [(8, 1 << 31)]
+
+
+def _assert_counter_premise(t, off):
+    first, last = we.prng_index_range(off, COUNTER_N, t)
+    if off == 1 << 31:
+        assert first > 1 << 33  # every block has a high word above 1
+    else:
+        assert first < 1 << 32 <= last  # i crosses 2^32 inside the call
+    assert off % 256 == 0
+
+
+@pytest.mark.parametrize("rounds", [20, 8])
+@pytest.mark.parametrize("t,off", COUNTER_CASES)
+def test_prng_coeffs_across_the_counter_high_word(t, off, rounds):
+    _assert_counter_premise(t, off)
+    co = coeff_block(COUNTER_N, t - 1, rounds=rounds, off=off)
+    want = c_oracle.prng_coeffs(KEY, 5, off, COUNTER_N, t - 1, rounds=rounds)
+    assert np.array_equal(block_limbs(co, COUNTER_N), want.transpose(1, 0, 2))
+
+
+@pytest.mark.parametrize("rounds", [20, 8])
+@pytest.mark.parametrize("t,off", COUNTER_CASES)
+def test_split_prng_across_the_counter_high_word(t, off, rounds):
+    _assert_counter_premise(t, off)
+    n = t + 1
+    sec = torch.from_numpy(secrets_int64(t + rounds, COUNTER_N)).to(dev())
+    shares = torch.empty((n, field.vec_bytes(COUNTER_N)), dtype=torch.uint8, device=dev())
+    _native.split_prng(sec, KEY, 5, rounds, off, shares, COUNTER_N, t, n)
+    want = c_oracle.split(sec.cpu().numpy(), c_oracle.prng_coeffs(KEY, 5, off, COUNTER_N, t - 1, rounds=rounds), t, n)
+    assert np.array_equal(block_limbs(shares, COUNTER_N), want)
+
+
+@pytest.mark.parametrize("cut", [256, 512])
+def test_split_prng_sharded_equals_unsharded_across_2_32(cut):
+    """test_split_prng_sharded_equals_unsharded with the cut beside the element
+    whose coefficient index reaches 2^32: each shard's elem_offset is large."""
+    t, n = 3, 5
+    off = we.prng_offset_below_2_32(t)
+    _assert_counter_premise(t, off)
+    N = COUNTER_N
+    sec = torch.from_numpy(secrets_int64(3, N)).to(dev())
+    whole = torch.empty((n, field.vec_bytes(N)), dtype=torch.uint8, device=dev())
+    _native.split_prng(sec, KEY, 9, 20, off, whole, N, t, n)
+    want = c_oracle.split(sec.cpu().numpy(), c_oracle.prng_coeffs(KEY, 9, off, N, t - 1), t, n)
+    assert np.array_equal(block_limbs(whole, N), want)
+    for lo, hi in ((0, cut), (cut, N)):
+        part = torch.empty((n, field.vec_bytes(hi - lo)), dtype=torch.uint8, device=dev())
+        _native.split_prng(sec[lo:hi].contiguous(), KEY, 9, 20, off + lo, part, hi - lo, t, n)
+        assert np.array_equal(block_limbs(part, hi - lo), want[:, lo:hi])
