@@ -51,6 +51,7 @@ EXPORTS = (
     "dn_mt19937_rt_rows_embedded", "dn_mt19937_spec_stats", "dn_mt19937_jump_poly",
     "dn_mt19937_split_many_scratch_bytes", "dn_mt19937_split_many_supported", "dn_mt19937_split_many_device",
     "dn_m521_reconstruct_many_scratch_bytes", "dn_m521_reconstruct_many", "dn_m521_sum_vecs",
+    "dn_m521_reconstruct_records",
 )
 
 
@@ -199,6 +200,11 @@ def _load(path: str) -> ctypes.CDLL:
     if hasattr(L, "dn_m521_sum_vecs"):
         L.dn_m521_sum_vecs.restype = i32
         L.dn_m521_sum_vecs.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p, u64, vp, u64, vp]
+    if hasattr(L, "dn_m521_reconstruct_records"):
+        L.dn_m521_reconstruct_records.restype = i32
+        L.dn_m521_reconstruct_records.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp),
+                                                  ctypes.POINTER(u64), ctypes.POINTER(Lagrange), vp, vp, vp, vp, u64,
+                                                  vp]
     L.dn_block_retired_bytes.restype = i32
     L.dn_block_retired_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.dn_block_probe_rows.restype = i32
@@ -380,6 +386,28 @@ def sum_vecs(ptrs: Sequence[int], negate: Optional[Sequence[bool]], out_ptr: int
     if neg is not None and len(neg) != m:
         raise ValueError("sum_vecs: one negate flag per input")
     check(L.dn_m521_sum_vecs((ctypes.c_void_p * max(m, 1))(*ptrs), neg, m, out_ptr, n_tiles, stream_ptr()))
+
+
+def reconstruct_records(wires: Sequence, xs: Sequence[int], w: Lagrange, bad, out_fe=None, out_u64=None,
+                        overflow=None, n: int = 0) -> None:
+    """Reconstruct straight from wire records (dn_m521_reconstruct_records):
+    wires[i] = (address of the packed records, their byte count, address of
+    uint64 / int64 offsets[n + 1]) of abscissa xs[i], w the weights of
+    `lagrange(xs, t)`, bad a device int32 / uint32 tensor [2] the kernel ADDS
+    its two counts to (unrepresentable records, records whose x is not xs[i]).
+    Outputs as `reconstruct`.  Does not synchronise."""
+    L = lib()
+    if not hasattr(L, "dn_m521_reconstruct_records"):
+        raise RuntimeError(f"{lib_path()} lacks dn_m521_reconstruct_records: rebuild the native library")
+    k = len(wires)
+    if k != w.k or k != len(xs):
+        raise ValueError("reconstruct_records: one wire and one abscissa per weight")
+    m = max(k, 1)
+    check(L.dn_m521_reconstruct_records((ctypes.c_void_p * m)(*[p for p, _, _ in wires]),
+                                        (ctypes.c_uint64 * m)(*[b for _, b, _ in wires]),
+                                        (ctypes.c_void_p * m)(*[o for _, _, o in wires]),
+                                        (ctypes.c_uint64 * m)(*[int(x) for x in xs]), ctypes.byref(w), _ptr(out_fe),
+                                        _ptr(out_u64), _ptr(overflow), _ptr(bad), n, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

@@ -141,6 +141,16 @@ def check_bad(bad) -> None:
         raise ValueError(f"decode_share_vec: {nbad} records with x > 8 bytes or y > 68 bytes")
 
 
+def check_bad_records(bad) -> None:
+    """Raise if a deferred `SecretShare.resolve_records_vec(..., bad=flag)` met
+    records it cannot represent (flag[0]) or records whose x is not their
+    wire's abscissa (flag[1]): one read-back of the two counts."""
+    nbad, nmis = (int(c) for c in bad.tolist())
+    if nbad or nmis:
+        raise ValueError(f"resolve_records_vec: {nbad} records with x > 8 bytes or y > 68 bytes, "
+                         f"{nmis} records whose x is not their wire's abscissa")
+
+
 def records_to_list(packed_host, offsets_host) -> List[bytes]:
     """Host copy -> the reference's List[bytes] (one record per element)."""
     buf = bytes(packed_host.numpy() if hasattr(packed_host, "numpy") else packed_host)

@@ -197,6 +197,37 @@ def _resolve_vectors(vecs: Sequence, xs: Sequence[int], n: int, threshold: int,
                         overflow=overflow, n=n)
 
 
+def _i64(x: int) -> int:
+    """A 64-bit abscissa as the int64 a decoded `xs` tensor holds for it."""
+    return x - (1 << 64) if x >= (1 << 63) else x
+
+
+def _first_record_xs(recs) -> List[int]:
+    """The abscissa in the header `[len(x)][x]` of every wire's first record
+    (`_bytes_to_share`, shamir.py:36-45): offsets[0:2] and at most 9 bytes per
+    wire, gathered on the device and read back in one copy."""
+    import torch
+
+    idx = torch.arange(9, device=recs[0][0].device)
+    heads, spans = [], []
+    for packed, offsets in recs:
+        spans.append(offsets[:2])
+        if packed.numel():
+            heads.append(packed[(offsets[0] + idx).clamp(0, packed.numel() - 1)].to(torch.int64))
+        else:
+            heads.append(torch.zeros(9, dtype=torch.int64, device=packed.device))
+    host = torch.cat(spans + heads).cpu().tolist()
+    k = len(recs)
+    xs = []
+    for i, (packed, _) in enumerate(recs):
+        o0, o1 = host[2 * i], host[2 * i + 1]
+        head = host[2 * k + 9 * i:2 * k + 9 * i + 9]
+        if not (0 <= o0 < o1 <= packed.numel()) or head[0] > 8 or 1 + head[0] > o1 - o0:
+            raise ValueError(f"resolve_records_vec: the first record of wire {i} has no readable x")
+        xs.append(int.from_bytes(bytes(head[1:1 + head[0]]), "big"))
+    return xs
+
+
 # ------------------------------------------------------------------ API
 class SecretShare(object):
     """Threshold-`threshold` Shamir scheme over GF(PRIME) (shamir.py:48-90)."""
@@ -484,6 +515,127 @@ class SecretShare(object):
         else:
             raise ValueError('resolve_shares_vec: out must be "int64" or "field"')
         return (res, over) if return_overflow else res
+
+    def resolve_records_vec(self, records, xs: Optional[Sequence[int]], n: int, *, out: str = "int64",
+                            return_overflow: bool = False, bad=None):
+        """Interpolate at 0 straight from wire records — `resolve_shares`
+        (shamir.py:68-90) takes the shares as they arrive, a list of
+        `_share_to_bytes` records; this is its vector form, in one launch and
+        without the k decoded vectors (dn_m521_reconstruct_records).
+
+        records  sequence of k (packed, offsets) pairs as
+                 `codec.encode_share_vec` returns them: packed a contiguous
+                 uint8 device tensor, offsets a contiguous int64 device tensor
+                 of at least n + 1 entries.  A `packed` view that is not 4-byte
+                 aligned is copied once, as decode_share_vec copies it
+        xs       the k abscissas; None takes each wire's x from its first
+                 record, as the reference takes it from the data — one
+                 read-back of offsets[0:2] and at most 9 record bytes per wire,
+                 the only form that synchronises before the launch
+        n        elements
+        out, return_overflow  as resolve_shares_vec
+        bad      None: one read-back after the launch, and ValueError naming
+                 both counts when a record cannot be represented (x > 8 bytes,
+                 y > 68 bytes, offsets decreasing or past the wire) or carries
+                 an x other than its wire's.  An int32 device tensor [2]: the
+                 two counts are ADDED to it on the device and the call does not
+                 synchronise; `codec.check_bad_records(bad)` raises later
+        Same checks, messages and exception types as `resolve_shares_vec`, all
+        before any device use.  The results are those of decode_share_vec on
+        every wire followed by resolve_shares_vec, bit for bit (an
+        unrepresentable record counts as y = 0 there and here).  Where the
+        native form does not apply (k > 16, an abscissa outside 64 bits) the
+        wires are decoded with decode_share_vec and interpolated by the grouped
+        full-width path: the same results, on the GPU (there the second count
+        comes from the decoded xs, so it also counts the unrepresentable
+        records, whose x the decoder leaves unparsed)."""
+        self._require_m521()
+        import torch
+
+        from . import codec
+
+        recs = [tuple(r) for r in records]
+        if any(len(r) != 2 for r in recs):
+            raise ValueError("resolve_records_vec: records must be (packed, offsets) pairs")
+        if xs is not None:
+            xs = [int(x) for x in xs]
+            if len(recs) != len(xs):
+                raise ValueError("resolve_records_vec: one abscissa per wire")
+            self._check_abscissas(xs)
+        elif not recs:
+            raise ValueError("not enough values to unpack (expected 2, got 0)")
+        if out not in ("int64", "field"):
+            raise ValueError('resolve_records_vec: out must be "int64" or "field"')
+        n = int(n)
+        if n < 0:
+            raise ValueError("resolve_records_vec: n must not be negative")
+        first = recs[0][0]
+        for packed, offsets in recs:
+            if not (isinstance(packed, torch.Tensor) and packed.dtype == torch.uint8 and packed.dim() == 1
+                    and packed.is_contiguous()):
+                raise ValueError("resolve_records_vec: packed records must be contiguous 1-D uint8 tensors")
+            if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1
+                    and offsets.is_contiguous()):
+                raise ValueError("resolve_records_vec: offsets must be contiguous 1-D int64 tensors")
+            if packed.device != first.device or offsets.device != first.device:
+                raise ValueError("resolve_records_vec: every wire's records and offsets must be on one device")
+            if offsets.numel() < n + 1:
+                raise ValueError(f"resolve_records_vec: offsets must hold n + 1 = {n + 1} entries, "
+                                 f"got {offsets.numel()}")
+        if bad is not None and not (isinstance(bad, torch.Tensor) and bad.dtype == torch.int32
+                                    and tuple(bad.shape) == (2,) and bad.is_contiguous()
+                                    and bad.device == first.device):
+            raise ValueError("resolve_records_vec: bad must be a contiguous int32 tensor [2] on the records' device")
+        if xs is None and n == 0:
+            raise ValueError("resolve_records_vec: xs=None needs a first record to read each abscissa from")
+        dev = _device()
+        if first.device != dev:
+            raise ValueError(f"resolve_records_vec: records must be on {dev}")
+        if xs is None:
+            xs = _first_record_xs(recs)
+            self._check_abscissas(xs)
+        k = len(xs)
+        checked = bad is None
+        if checked:
+            bad = torch.zeros(2, dtype=torch.int32, device=dev)
+        vb = field.vec_bytes(n)
+        over = torch.zeros(1, dtype=torch.int32, device=dev) if return_overflow else None
+        as_int = out == "int64"
+        res = (torch.empty(n, dtype=torch.int64, device=dev) if as_int
+               else torch.empty(vb, dtype=torch.uint8, device=dev))
+        if k <= _native.MAX_RESOLVE and all(0 <= x < (1 << 64) for x in xs):
+            # the kernels load dwords: one aligned device copy of a misaligned view
+            recs = [(p.clone() if p.data_ptr() & 3 else p, o) for p, o in recs]
+            w = _native.lagrange(xs, self.threshold)
+            _native.reconstruct_records([(p.data_ptr(), p.numel(), o.data_ptr()) for p, o in recs], xs, w, bad,
+                                        out_fe=None if as_int else res, out_u64=res if as_int else None,
+                                        overflow=over, n=n)
+        else:  # decode every wire, then the grouped full-width interpolation: the same results
+            vecs = []
+            for (p, o), x in zip(recs, xs):
+                v, got = codec.decode_share_vec(p, o, n, bad=bad[0:1])
+                if 0 <= x < (1 << 64):  # (a record's x is 64 bits at most: a larger abscissa never matches)
+                    bad[1:2] += (got != _i64(x)).sum().to(torch.int32)
+                else:
+                    bad[1:2] += n
+                vecs.append(v)
+            _resolve_vectors(vecs, xs, n, self.threshold, out_fe=None if as_int else res,
+                             out_u64=res if as_int else None, overflow=over)
+        if checked:
+            codec.check_bad_records(bad)
+        return (res, over) if return_overflow else res
+
+    def _check_abscissas(self, xs: Sequence[int]) -> None:
+        """resolve_shares' checks on the abscissas (shamir.py:70-83), with its messages."""
+        if len(xs) == 0:
+            raise ValueError("not enough values to unpack (expected 2, got 0)")
+        k = len(xs)
+        if k < self.threshold:
+            raise ValueError("need at least {} shares".format(self.threshold))
+        if k != len(set(xs)):
+            raise ValueError("shares must be distinct")
+        if k == 1:
+            raise TypeError("reduce() of empty iterable with no initial value")
 
     def resolve_shares_vec_many(self, shares, xs: Sequence[int], ns: Sequence[int], *, out: str = "int64",
                                 outs=None, return_overflow: bool = False):

@@ -472,6 +472,46 @@ int dn_m521_encode_shares(const void* vec, uint64_t n_elem, uint64_t x, uint64_t
 int dn_m521_decode_shares(const uint8_t* in, uint64_t in_bytes, const uint64_t* offsets, uint64_t n_elem, void* vec,
                           uint64_t* xs, uint32_t* bad_count, void* stream);
 
+/*
+ * Reconstruct straight from wire records: what `resolve_shares` does with the
+ * shares as they arrive (shamir.py:68-90 over `_bytes_to_share`, :36-45), for
+ * whole vectors and in one launch.  Wire i is the packed record stream of
+ * abscissa xs[i] (dn_m521_encode_shares' output: records [len(xb)][xb][yb]
+ * back to back with offsets[n_elem + 1]); element e of the result is
+ *     sum_i lambda_i * (y of record e of wire i mod p)  mod p, canonical.
+ * Outputs and *overflow_count are bit for bit those of dn_m521_decode_shares
+ * on every wire followed by dn_m521_reconstruct, without the k intermediate
+ * tiled vectors: each record is parsed as the decoder parses it (x up to 8
+ * bytes, leading zero bytes of y allowed, y up to 68 significant bytes reduced
+ * mod p, untrusted offsets) and interpolated in registers.
+ *   in, in_bytes, offsets, xs  HOST arrays of w->k entries: in[i] DEVICE bytes
+ *                 (4-byte aligned; a 16-byte aligned wire takes the wide
+ *                 path, wire by wire), in_bytes[i] their count, offsets[i]
+ *                 DEVICE uint64[n_elem + 1], xs[i] the abscissa wire i's
+ *                 records should carry (the x *w was computed for)
+ *   w             weights of dn_m521_lagrange for xs, 2 <= w->k <= 16
+ *   out_fe, out_u64, overflow_count  as dn_m521_reconstruct (either output
+ *                 and the counter may be NULL, not both outputs)
+ *   bad_counts    DEVICE uint32[2], ADDED to: [0] records the decoder cannot
+ *                 represent (the sum of the k decodes' bad counts; such a
+ *                 record contributes y = 0, as its decoded vector would),
+ *                 [1] representable records whose x is not xs[i] (their y is
+ *                 used all the same: the two-step route returns the xs and
+ *                 leaves that comparison to the caller)
+ * Nothing outside in[i][0, in_bytes[i]) and offsets[i][0, n_elem] is read.
+ * n_elem == 0 returns DN_OK and touches no pointer.  DN_ERR_ARG, before any
+ * device call: a null pointer, a wire that is not 4-byte aligned, w->k
+ * outside 2..16, malformed weights, no output.  The wire descriptors and the
+ * weights travel in the kernel arguments: no device table, no staging buffer.
+ * Does not synchronise `stream`; can be captured into a graph.
+ * Replaces shamir.py:68-90 over records parsed by :36-45.
+ */
+int dn_m521_reconstruct_records(const uint8_t* const* in, const uint64_t* in_bytes,
+                                const uint64_t* const* offsets, const uint64_t* xs,
+                                const dn_m521_lagrange_t* w, void* out_fe, int64_t* out_u64,
+                                uint32_t* overflow_count, uint32_t* bad_counts /* device uint32[2] */,
+                                uint64_t n_elem, void* stream);
+
 /* Thread-local message of the last failure (never NULL). */
 const char* dn_last_error(void);
 
