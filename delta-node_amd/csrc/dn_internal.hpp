@@ -1,10 +1,14 @@
 // dn_internal.hpp — shared declarations of the native library (not part of the C-ABI).
 #pragma once
 
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 
 #include "dn_shamir.h"
+
+struct ihipEvent_t;   // hipEvent_t = ihipEvent_t*
+struct ihipStream_t;  // hipStream_t = ihipStream_t*
 
 namespace dn {
 // A/B tuning knobs (grid cap, wave schedule, store policy, kernel variants).
@@ -39,6 +43,28 @@ inline bool fd_needs_fold(int t, int n) {
 
 // Compute units of the current device (cached per device; shamir_m521.hip).
 int device_cu_count();
+
+// Pinned staging for a table that an entry point uploads WITHOUT synchronising
+// its stream (dn_m521_reconstruct_many, dn_m521_encode_shares_many; the pool is
+// in shamir_m521.hip).  A buffer carries an event; whoever used it records the
+// event on its stream behind the copy before handing the buffer back, and it
+// is handed out again only once that event has completed (or to nobody: a busy
+// buffer is skipped and a new one made).  So a buffer is never rewritten while
+// a copy may still read it, whichever thread or stream asks next: buffers are
+// not tied to a stream, and one is in a single call's hands between take() and
+// give().  (ev / the stream: hipEvent_t / hipStream_t, named by their
+// underlying types so that this header needs no HIP header.)
+struct StageBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  ::ihipEvent_t* ev = nullptr;
+  int dev = -1;
+};
+// A buffer of at least `need` bytes whose last copy has completed; .p null on failure.
+StageBuf stage_take(size_t need);
+// Back to the pool; `s`: the stream whose queued copies read the buffer (null
+// pointer argument: none were queued).
+void stage_give(StageBuf b, ::ihipStream_t* const* s);
 
 // MT19937 jump-ahead (host_mt_jump.cpp): substream length in words, the most
 // substreams the jump table covers, a window stepped forward on the host, and

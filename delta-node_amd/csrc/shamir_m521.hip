@@ -1020,22 +1020,9 @@ static int recon_set_weights(ReconArgs& a, const dn_m521_lagrange_t* w, const ch
   return DN_OK;
 }
 
-// Pinned staging for a table that an entry point uploads WITHOUT synchronising
-// its stream (dn_m521_reconstruct_many).  A buffer carries an event; whoever
-// used it records the event on its stream behind the copy before handing the
-// buffer back, and it is handed out again only once that event has completed
-// (or to nobody: a busy buffer is skipped and a new one made).  So a buffer is
-// never rewritten while a copy may still read it, whichever thread or stream
-// asks next: buffers are not tied to a stream, and one is in a single call's
-// hands between take() and give().  The pool is leaked on purpose (the HIP
-// runtime may be torn down before static destructors run).
-struct StageBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  hipEvent_t ev = nullptr;
-  int dev = -1;
-};
-
+// The pool of pinned staging buffers behind stage_take / stage_give
+// (dn_internal.hpp).  It is leaked on purpose (the HIP runtime may be torn
+// down before static destructors run).
 struct StagePool {
   std::mutex m;
   std::vector<StageBuf> bufs;  // not in a call's hands (their events may be pending)
@@ -1047,7 +1034,7 @@ static StagePool& stage_pool() {
 }
 
 // A buffer of at least `need` bytes whose last copy has completed; .p null on failure.
-static StageBuf stage_take(size_t need) {
+StageBuf stage_take(size_t need) {
   StageBuf b;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return b;
@@ -1079,7 +1066,7 @@ static StageBuf stage_take(size_t need) {
 
 // Back to the pool; `s`: the stream whose queued copies read the buffer (null
 // pointer argument: none were queued).
-static void stage_give(StageBuf b, const hipStream_t* s) {
+void stage_give(StageBuf b, const hipStream_t* s) {
   if (s && hipEventRecord(b.ev, *s) != hipSuccess) {
     (void)hipStreamSynchronize(*s);  // no marker behind the copy: wait for it instead
   }

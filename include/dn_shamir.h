@@ -473,6 +473,46 @@ int dn_m521_decode_shares(const uint8_t* in, uint64_t in_bytes, const uint64_t* 
                           uint64_t* xs, uint32_t* bad_count, void* stream);
 
 /*
+ * Encode share rows of a LIST of tensors into one wire per row
+ * (shamir.py:28-33 `_share_to_bytes`, over the tensors' concatenation).  Tensor
+ * j has n_elem[j] elements and its own block of tiled share rows (what
+ * dn_mt19937_split_many_device leaves): row r at blocks[j] + r * pitches[j].
+ * Wire i encodes row rows[i] of every block under abscissa xs[i]: its packed
+ * stream is dn_m521_encode_shares(row rows[i] of tensor 0, n_0, xs[i]) ||
+ * (... of tensor 1 ...) || ..., tensors without elements contributing nothing,
+ * and offsets[i][e], e in [0, n_total], is the byte offset of the record of
+ * global element e (concatenation order, n_total = sum n_elem[j]);
+ * offsets[i][n_total] is the wire's length, also written to totals[i].
+ * Records carry no tile structure, so such a wire is the wire of ONE vector of
+ * n_total elements to dn_m521_decode_shares / dn_m521_reconstruct_records.
+ * Words past n_elem[j] in a block's last tile never influence the result (the
+ * block covers them: pitches[j] >= dn_m521_vec_bytes(n_elem[j])).
+ *   n_elem, blocks, pitches  HOST arrays of n_segments entries (blocks[j]
+ *                 DEVICE, 4-byte aligned like pitches[j]; ignored where
+ *                 n_elem[j] == 0)
+ *   rows, xs, offsets, outs, capacities  HOST arrays of n_rows entries:
+ *                 offsets[i] DEVICE uint64[n_total + 1], outs[i] DEVICE bytes,
+ *                 4-byte aligned (a 16-byte aligned one takes the wide store
+ *                 path, wire by wire), capacities[i] >=
+ *                 dn_m521_encoded_capacity(n_total, xs[i])
+ *   totals        DEVICE uint64[n_rows]
+ *   scratch       device memory of dn_m521_encode_many_scratch_bytes(
+ *                 n_segments, sum_j ceil(n_elem[j] / 256), n_rows) bytes: the
+ *                 segment table and 8 bytes per (tile, wire)
+ * A list without elements, or n_rows == 0, returns DN_OK and touches nothing.
+ * DN_ERR_ARG, before any device call: a null pointer, a misaligned block or
+ * `out`, a capacity or scratch too small, more than 65536 tensors.  The table
+ * is uploaded from a pinned staging buffer by hipMemcpyAsync on `stream`; three
+ * launches per 16 wires.  Does not synchronise `stream`.
+ */
+uint64_t dn_m521_encode_many_scratch_bytes(uint64_t n_segments, uint64_t total_tiles, uint64_t n_rows);
+int dn_m521_encode_shares_many(const uint64_t* n_elem, const void* const* blocks, const uint64_t* pitches,
+                               uint64_t n_segments, const uint32_t* rows, const uint64_t* xs,
+                               uint64_t* const* offsets, uint8_t* const* outs, const uint64_t* capacities,
+                               uint64_t n_rows, uint64_t* totals, void* scratch, uint64_t scratch_bytes,
+                               void* stream);
+
+/*
  * Reconstruct straight from wire records: what `resolve_shares` does with the
  * shares as they arrive (shamir.py:68-90 over `_bytes_to_share`, :36-45), for
  * whole vectors and in one launch.  Wire i is the packed record stream of
