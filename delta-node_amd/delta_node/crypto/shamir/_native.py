@@ -51,7 +51,7 @@ EXPORTS = (
     "dn_mt19937_rt_rows_embedded", "dn_mt19937_spec_stats", "dn_mt19937_jump_poly",
     "dn_mt19937_split_many_scratch_bytes", "dn_mt19937_split_many_supported", "dn_mt19937_split_many_device",
     "dn_m521_reconstruct_many_scratch_bytes", "dn_m521_reconstruct_many", "dn_m521_sum_vecs",
-    "dn_m521_reconstruct_records",
+    "dn_m521_reconstruct_records", "dn_m521_sum_records",
 )
 
 
@@ -205,6 +205,10 @@ def _load(path: str) -> ctypes.CDLL:
         L.dn_m521_reconstruct_records.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp),
                                                   ctypes.POINTER(u64), ctypes.POINTER(Lagrange), vp, vp, vp, vp, u64,
                                                   vp]
+    if hasattr(L, "dn_m521_sum_records"):
+        L.dn_m521_sum_records.restype = i32
+        L.dn_m521_sum_records.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp), u64, u64,
+                                          ctypes.c_char_p, vp, vp, vp, u64, vp]
     L.dn_block_retired_bytes.restype = i32
     L.dn_block_retired_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.dn_block_probe_rows.restype = i32
@@ -408,6 +412,32 @@ def reconstruct_records(wires: Sequence, xs: Sequence[int], w: Lagrange, bad, ou
                                         (ctypes.c_void_p * m)(*[o for _, _, o in wires]),
                                         (ctypes.c_uint64 * m)(*[int(x) for x in xs]), ctypes.byref(w), _ptr(out_fe),
                                         _ptr(out_u64), _ptr(overflow), _ptr(bad), n, stream_ptr()))
+
+
+def sum_records(wires: Sequence, x: int, negate: Optional[Sequence[bool]], bad, out, acc=None, n: int = 0) -> None:
+    """out = acc + sum_i +-(y of wire i's records) mod p, straight from wire
+    records (dn_m521_sum_records): wires[i] = (address of the packed records,
+    their byte count, address of uint64 / int64 offsets[n + 1]), x the
+    abscissa every record should carry, negate m flags (true: subtract) or
+    None, bad a device int32 / uint32 tensor [2] the kernel ADDS its two counts
+    to (unrepresentable records, records whose x is not x), out / acc tiled
+    uint8 device vectors of n elements (acc may be out, or None).  Any m >= 1:
+    the entry point chains launches of DN_M521_SUM_RECORDS_GROUP wires.  Does
+    not synchronise."""
+    L = lib()
+    if not hasattr(L, "dn_m521_sum_records"):
+        raise RuntimeError(f"{lib_path()} lacks dn_m521_sum_records: rebuild the native library")
+    m = len(wires)
+    neg = None if negate is None else bytes(1 if f else 0 for f in negate)
+    if neg is not None and len(neg) != m:
+        raise ValueError("sum_records: one negate flag per wire")
+    if not 0 <= int(x) < (1 << 64):
+        raise ValueError("sum_records: x must fit 64 bits")
+    k = max(m, 1)
+    check(L.dn_m521_sum_records((ctypes.c_void_p * k)(*[p for p, _, _ in wires]),
+                                (ctypes.c_uint64 * k)(*[b for _, b, _ in wires]),
+                                (ctypes.c_void_p * k)(*[o for _, _, o in wires]), m, int(x), neg, _ptr(acc),
+                                _ptr(out), _ptr(bad), n, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

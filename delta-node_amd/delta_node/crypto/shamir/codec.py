@@ -278,13 +278,14 @@ def check_bad(bad) -> None:
         raise ValueError(f"decode_share_vec: {nbad} records with x > 8 bytes or y > 68 bytes")
 
 
-def check_bad_records(bad) -> None:
-    """Raise if a deferred `SecretShare.resolve_records_vec(..., bad=flag)` met
+def check_bad_records(bad, what: str = "resolve_records_vec") -> None:
+    """Raise if a deferred `SecretShare.resolve_records_vec(..., bad=flag)` (or
+    `sum_records_vec`: what="sum_records_vec" names it in the message) met
     records it cannot represent (flag[0]) or records whose x is not their
     wire's abscissa (flag[1]): one read-back of the two counts."""
     nbad, nmis = (int(c) for c in bad.tolist())
     if nbad or nmis:
-        raise ValueError(f"resolve_records_vec: {nbad} records with x > 8 bytes or y > 68 bytes, "
+        raise ValueError(f"{what}: {nbad} records with x > 8 bytes or y > 68 bytes, "
                          f"{nmis} records whose x is not their wire's abscissa")
 
 

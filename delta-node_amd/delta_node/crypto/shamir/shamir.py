@@ -202,7 +202,7 @@ def _i64(x: int) -> int:
     return x - (1 << 64) if x >= (1 << 63) else x
 
 
-def _first_record_xs(recs) -> List[int]:
+def _first_record_xs(recs, what: str = "resolve_records_vec") -> List[int]:
     """The abscissa in the header `[len(x)][x]` of every wire's first record
     (`_bytes_to_share`, shamir.py:36-45): offsets[0:2] and at most 9 bytes per
     wire, gathered on the device and read back in one copy."""
@@ -223,7 +223,7 @@ def _first_record_xs(recs) -> List[int]:
         o0, o1 = host[2 * i], host[2 * i + 1]
         head = host[2 * k + 9 * i:2 * k + 9 * i + 9]
         if not (0 <= o0 < o1 <= packed.numel()) or head[0] > 8 or 1 + head[0] > o1 - o0:
-            raise ValueError(f"resolve_records_vec: the first record of wire {i} has no readable x")
+            raise ValueError(f"{what}: the first record of wire {i} has no readable x")
         xs.append(int.from_bytes(bytes(head[1:1 + head[0]]), "big"))
     return xs
 
@@ -786,4 +786,124 @@ class SecretShare(object):
         if out is None:
             out = torch.empty_like(first)
         _native.sum_vecs([b.data_ptr() for b in blocks], negate, out.data_ptr(), first.numel() // field.TILE_BYTES)
+        return out
+
+    def sum_records_vec(self, records, x: Optional[int], n: int, *, signs=None, acc=None, out=None, bad=None):
+        """`sum_shares_vec` straight from wire records — the party-side sum as
+        the shares arrive: party x holds share x of every member's tensor as m
+        wires, and their sum mod p is share x of the tensors' sum.  One launch,
+        without the m decoded vectors (dn_m521_sum_records).
+
+        records  sequence of m >= 1 (packed, offsets) pairs as
+                 `codec.encode_share_vec` returns them: packed a contiguous
+                 uint8 device tensor, offsets a contiguous int64 device tensor
+                 of at least n + 1 entries.  A `packed` view that is not 4-byte
+                 aligned is copied once, as decode_share_vec copies it
+        x        the abscissa every record should carry (below 2^64); None
+                 takes it from each wire's first record — one read-back of
+                 offsets[0:2] and at most 9 record bytes per wire, the only form
+                 that synchronises before the launch — and raises ValueError if
+                 the wires disagree (it needs n > 0)
+        n        elements
+        signs    optional m values, each +1 or -1 (-1: subtract that member),
+                 as in sum_shares_vec
+        acc      optional tiled vector added to the sum: contiguous uint8
+                 [vec_bytes(n)] on the records' device.  It may be `out`
+                 (accumulate as members' wires arrive)
+        out      optional output of the same form; default: a fresh tensor.
+                 Every byte is written: the lanes past n of the last tile as
+                 zero, whatever acc holds there
+        bad      None: one read-back after the launch, and ValueError naming
+                 both counts when a record cannot be represented (x > 8 bytes,
+                 y > 68 bytes, offsets decreasing or past the wire) or carries
+                 an x other than `x`.  An int32 device tensor [2]: the two
+                 counts are ADDED to it on the device and the call does not
+                 synchronise; `codec.check_bad_records(bad,
+                 what="sum_records_vec")` raises later
+        Returns `out`: canonical residues, bit for bit those of
+        decode_share_vec on every wire followed by sum_shares_vec (an
+        unrepresentable record counts as y = 0 there and here).  Every argument
+        error is raised before any device use; n = 0 returns an empty vector.
+        Uses neither self.threshold nor self.random.  Any m: beyond
+        DN_M521_SUM_RECORDS_GROUP wires the native entry point chains launches
+        that accumulate into `out`.
+
+        There is no tensor-list form because none is needed: the concatenated
+        wire of `codec.encode_shares_many` IS the wire of one n_total-element
+        vector, so the m members' list wires are summed by this method with
+        n = n_total, and the sum re-encoded with `codec.encode_share_vec(sum,
+        n_total, x)` is what `resolve_records_vec(..., n_total)` reads."""
+        self._require_m521()
+        import torch
+
+        from . import codec
+
+        what = "sum_records_vec"
+        recs = [tuple(r) for r in records]
+        if any(len(r) != 2 for r in recs):
+            raise ValueError(f"{what}: records must be (packed, offsets) pairs")
+        if not recs:
+            raise ValueError(f"{what}: no records")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"{what}: n must not be negative")
+        first = recs[0][0]
+        for packed, offsets in recs:
+            if not (isinstance(packed, torch.Tensor) and packed.dtype == torch.uint8 and packed.dim() == 1
+                    and packed.is_contiguous()):
+                raise ValueError(f"{what}: packed records must be contiguous 1-D uint8 tensors")
+            if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1
+                    and offsets.is_contiguous()):
+                raise ValueError(f"{what}: offsets must be contiguous 1-D int64 tensors")
+            if packed.device != first.device or offsets.device != first.device:
+                raise ValueError(f"{what}: every wire's records and offsets must be on one device")
+            if offsets.numel() < n + 1:
+                raise ValueError(f"{what}: offsets must hold n + 1 = {n + 1} entries, got {offsets.numel()}")
+        if x is not None:
+            if isinstance(x, bool) or not isinstance(x, numbers.Integral):
+                raise ValueError(f"{what}: x must be an integer or None")
+            x = int(x)
+            if not 0 <= x < (1 << 64):
+                raise ValueError(f"{what}: x must fit 64 bits")
+        elif n == 0:
+            raise ValueError(f"{what}: x=None needs a first record to read the abscissa from")
+        negate = None
+        if signs is not None:
+            signs = list(signs)
+            if len(signs) != len(recs):
+                raise ValueError(f"{what}: {len(signs)} signs for {len(recs)} wires")
+            if any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s not in (1, -1) for s in signs):
+                raise ValueError(f"{what}: signs must be +1 or -1")
+            negate = [s < 0 for s in signs]
+        vb = field.vec_bytes(n)
+        for name, t in (("acc", acc), ("out", out)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8
+                                      and tuple(t.shape) == (vb,) and t.is_contiguous()
+                                      and t.device == first.device):
+                raise ValueError(f"{what}: {name} must be a contiguous uint8 tensor [{vb}] on the records' device")
+        if bad is not None and not (isinstance(bad, torch.Tensor) and bad.dtype == torch.int32
+                                    and tuple(bad.shape) == (2,) and bad.is_contiguous()
+                                    and bad.device == first.device):
+            raise ValueError(f"{what}: bad must be a contiguous int32 tensor [2] on the records' device")
+        dev = _device()
+        if first.device != dev:
+            raise ValueError(f"{what}: records must be on {dev}")
+        if x is None:
+            got = _first_record_xs(recs, what)
+            if len(set(got)) != 1:
+                raise ValueError(f"{what}: the wires' first records carry different abscissas: {got}")
+            x = got[0]
+        if out is None:
+            out = torch.empty(vb, dtype=torch.uint8, device=dev)
+        if n == 0:
+            return out
+        checked = bad is None
+        if checked:
+            bad = torch.zeros(2, dtype=torch.int32, device=dev)
+        # the kernel loads dwords: one aligned device copy of a misaligned view
+        recs = [(p.clone() if p.data_ptr() & 3 else p, o) for p, o in recs]
+        _native.sum_records([(p.data_ptr(), p.numel(), o.data_ptr()) for p, o in recs], x, negate, bad, out, acc=acc,
+                            n=n)
+        if checked:
+            codec.check_bad_records(bad, what=what)
         return out

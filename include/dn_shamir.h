@@ -552,6 +552,55 @@ int dn_m521_reconstruct_records(const uint8_t* const* in, const uint64_t* in_byt
                                 uint32_t* overflow_count, uint32_t* bad_counts /* device uint32[2] */,
                                 uint64_t n_elem, void* stream);
 
+/*
+ * Sum of share wires: the party-side step of share-domain aggregation taken
+ * straight from the records.  Party x holds share x of every member's tensor
+ * as m wires (dn_m521_encode_shares' output: records [len(xb)][xb][yb] back to
+ * back with offsets[n_elem + 1]); element e of the result is
+ *     out_e = (acc_e + sum_i +-(y of record e of wire i mod p))  mod p, canonical,
+ * in the tiled layout.  `out` is bit for bit dn_m521_decode_shares on every
+ * wire followed by dn_m521_sum_vecs (over acc and the m decoded vectors),
+ * without the m intermediate tiled vectors: each record is parsed as the
+ * decoder parses it (x up to 8 bytes, leading zero bytes of y allowed, y up to
+ * 68 significant bytes reduced mod p, untrusted offsets) and added in
+ * registers.  No reference counterpart: the reference sums masked results,
+ * coord/horizontal/agg.py:227-251, never shares.
+ *   in, in_bytes, offsets  HOST arrays of m entries: in[i] DEVICE bytes (4-byte
+ *                 aligned; a 16-byte aligned wire takes the wide path, wire by
+ *                 wire), in_bytes[i] their count, offsets[i] DEVICE
+ *                 uint64[n_elem + 1], 8-byte aligned
+ *   x             the abscissa every record should carry
+ *   negate        HOST array of m flags (non-zero: wire i is subtracted), or NULL
+ *   acc           DEVICE tiled vector of n_elem elements added to the sum
+ *                 (values < 2^521: bits 9..15 of the top plane are ignored), or
+ *                 NULL.  It may equal `out` (accumulate as members' wires
+ *                 arrive); overlapping `out` without being equal to it is
+ *                 DN_ERR_ARG
+ *   out           DEVICE, dn_m521_vec_bytes(n_elem) bytes.  Every byte is
+ *                 written: lanes >= n_elem of the last tile are written as
+ *                 zero, whatever acc holds there.  Nothing outside is written
+ *   bad_counts    DEVICE uint32[2], ADDED to: [0] records the decoder cannot
+ *                 represent (the sum of the m decodes' bad counts; such a
+ *                 record contributes y = 0, as its decoded vector would — under
+ *                 a negative sign p, which is 0 mod p), [1] representable
+ *                 records whose x is not `x` (their y is used all the same)
+ * Nothing outside in[i][0, in_bytes[i]) and offsets[i][0, n_elem] is read.
+ * One launch takes DN_M521_SUM_RECORDS_GROUP wires (64: the wire descriptors,
+ * sign bits and alignment bits travel in the kernel arguments, 1.6 KB of the
+ * 4 KB segment — no device table, no staging buffer); a longer list is chained:
+ * launch 1 writes `out` (from acc if given), each later launch adds the next
+ * group onto `out`.  Every launch ends canonical, so the result does not
+ * depend on where the group boundaries fall.  n_elem == 0 returns DN_OK and
+ * touches no pointer.  DN_ERR_ARG, before any device call: m == 0, a null
+ * pointer, a wire that is not 4-byte aligned, offsets that are not 8-byte
+ * aligned (the message names the wire), 2^31 tiles or more.  Does not
+ * synchronise `stream`; can be captured into a graph.
+ */
+#define DN_M521_SUM_RECORDS_GROUP 64
+int dn_m521_sum_records(const uint8_t* const* in, const uint64_t* in_bytes, const uint64_t* const* offsets,
+                        uint64_t m, uint64_t x, const uint8_t* negate, const void* acc, void* out,
+                        uint32_t* bad_counts /* device uint32[2] */, uint64_t n_elem, void* stream);
+
 /* Thread-local message of the last failure (never NULL). */
 const char* dn_last_error(void);
 
