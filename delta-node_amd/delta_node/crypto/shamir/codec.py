@@ -10,16 +10,24 @@ dn_m521_decode_shares); `records_to_list` turns a host copy into the
 reference's List[bytes] when a caller needs it.  `encode_shares_many` is the
 list form: the wires of a tensor list's share rows (make_shares_vec_many's
 blocks), each the tensors' records back to back, in three launches.
+
+A wire frame carries one wire and its record lengths in one buffer, so that
+the offsets reach the receiver: `encode_share_frame` / `encode_frames_many`
+encode straight into frames, `open_frames` turns received frames back into
+(packed, offsets) with one validated scan, `frame_fields_host` parses a host
+copy with numpy alone.
 """
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 from . import _native, field
 
 EXPORTS = ("dn_m521_codec_scratch_bytes", "dn_m521_encoded_capacity", "dn_m521_encode_shares",
-           "dn_m521_decode_shares", "dn_m521_encode_many_scratch_bytes", "dn_m521_encode_shares_many")
+           "dn_m521_decode_shares", "dn_m521_encode_many_scratch_bytes", "dn_m521_encode_shares_many",
+           "dn_m521_frame_records_offset", "dn_m521_frame_capacity", "dn_m521_frame_finish",
+           "dn_m521_frame_scratch_bytes", "dn_m521_frame_open")
 
 
 def _lib():
@@ -42,6 +50,18 @@ def _lib():
                                                      ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(u64),
                                                      ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(u64), u64,
                                                      vp, vp, u64, vp]
+        if hasattr(L, "dn_m521_frame_open"):
+            L.dn_m521_frame_records_offset.restype = u64
+            L.dn_m521_frame_records_offset.argtypes = [u64]
+            L.dn_m521_frame_capacity.restype = u64
+            L.dn_m521_frame_capacity.argtypes = [u64, u64]
+            L.dn_m521_frame_finish.restype = i32
+            L.dn_m521_frame_finish.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(u64), u64, u64, vp]
+            L.dn_m521_frame_scratch_bytes.restype = u64
+            L.dn_m521_frame_scratch_bytes.argtypes = [u64, u64]
+            L.dn_m521_frame_open.restype = i32
+            L.dn_m521_frame_open.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64), u64, u64,
+                                             ctypes.POINTER(vp), vp, vp, u64, vp]
         L._dn_codec_bound = True
     return L
 
@@ -148,6 +168,41 @@ def encode_shares_many(blocks, ns: Sequence[int], xs: Optional[Sequence[int]] = 
     import torch
 
     what = "encode_shares_many"
+    ns, ptrs, pitches, tiles, xs, rows, dev = _many_args(what, blocks, ns, xs, rows, outs, offsets)
+    if not xs:
+        return []
+    n_total = sum(ns)
+    dev = _many_device(what, dev)
+    L = _lib()
+    if not hasattr(L, "dn_m521_encode_shares_many"):
+        raise RuntimeError(f"{_native.lib_path()} lacks dn_m521_encode_shares_many: rebuild the native library")
+    m = len(xs)
+    caps = [int(L.dn_m521_encoded_capacity(n_total, x)) for x in xs]
+    packed, offs = [], []
+    for i in range(m):
+        o = _out(None if outs is None else outs[i], max(caps[i], 1), torch.uint8, dev, f"{what} outs[{i}]")
+        if o.data_ptr() & 3:
+            raise ValueError(f"{what} outs[{i}]: the buffer must be 4-byte aligned (the encoder stores dwords)")
+        packed.append(o)
+        # every entry is written by the encoder (offsets[n_total] by the list's last element)
+        offs.append(_out(None if offsets is None else offsets[i], n_total + 1, torch.int64, dev,
+                         f"{what} offsets[{i}]")[: n_total + 1])
+    if n_total == 0:
+        for o in offs:
+            o.zero_()
+        return [(p[:0] if trim else p, o) for p, o in zip(packed, offs)]
+    totals = _encode_many(L, ns, ptrs, pitches, tiles, xs, rows, packed, offs, caps, dev)
+    if trim:
+        packed = [p[:t] for p, t in zip(packed, totals.tolist())]  # one read-back for all wires
+    return list(zip(packed, offs))
+
+
+def _many_args(what: str, blocks, ns, xs, rows, outs, offsets):
+    """The argument rules of encode_shares_many (and encode_frames_many), no
+    device use: (ns, block addresses, pitches, tiles, xs, rows, the blocks'
+    device or None for an empty list)."""
+    import torch
+
     blocks, ns = list(blocks), [int(n) for n in ns]
     if len(blocks) != len(ns):
         raise ValueError(f"{what}: {len(blocks)} blocks for {len(ns)} sizes")
@@ -186,32 +241,24 @@ def encode_shares_many(blocks, ns: Sequence[int], xs: Optional[Sequence[int]] = 
     for name, bufs in (("outs", outs), ("offsets", offsets)):
         if bufs is not None and len(bufs) != len(xs):
             raise ValueError(f"{what}: {len(bufs)} {name} for {len(xs)} abscissas")
-    if not xs:
-        return []
-    n_total = sum(ns)
+    return ns, ptrs, pitches, tiles, xs, rows, dev
+
+
+def _many_device(what: str, dev):
+    """The device of a tensor list's blocks (the current one for an empty list)."""
     if dev is None or dev.type != "cuda":
         if dev is not None:
             raise ValueError(f"{what}: the blocks must be on a HIP device (they are on {dev})")
         dev = _native.require_device()
-    L = _lib()
-    if not hasattr(L, "dn_m521_encode_shares_many"):
-        raise RuntimeError(f"{_native.lib_path()} lacks dn_m521_encode_shares_many: rebuild the native library")
-    m = len(xs)
-    caps = [int(L.dn_m521_encoded_capacity(n_total, x)) for x in xs]
-    packed, offs = [], []
-    for i in range(m):
-        o = _out(None if outs is None else outs[i], max(caps[i], 1), torch.uint8, dev, f"{what} outs[{i}]")
-        if o.data_ptr() & 3:
-            raise ValueError(f"{what} outs[{i}]: the buffer must be 4-byte aligned (the encoder stores dwords)")
-        packed.append(o)
-        # every entry is written by the encoder (offsets[n_total] by the list's last element)
-        offs.append(_out(None if offsets is None else offsets[i], n_total + 1, torch.int64, dev,
-                         f"{what} offsets[{i}]")[: n_total + 1])
-    if n_total == 0:
-        for o in offs:
-            o.zero_()
-        return [(p[:0] if trim else p, o) for p, o in zip(packed, offs)]
-    nseg = len(ns)
+    return dev
+
+
+def _encode_many(L, ns, ptrs, pitches, tiles, xs, rows, packed, offs, caps, dev):
+    """dn_m521_encode_shares_many over validated arguments (n_total > 0): wire
+    i into packed[i] / offs[i]; returns the device int64[m] of the wires' lengths."""
+    import torch
+
+    nseg, m = len(ns), len(xs)
     sb = int(L.dn_m521_encode_many_scratch_bytes(nseg, tiles, m))
     scratch = _scratch(dev, sb)
     totals = torch.empty(m, dtype=torch.int64, device=dev)
@@ -222,9 +269,7 @@ def encode_shares_many(blocks, ns: Sequence[int], xs: Optional[Sequence[int]] = 
         (ctypes.c_uint32 * m)(*rows), wu64(*xs), wvp(*[o.data_ptr() for o in offs]),
         wvp(*[p.data_ptr() for p in packed]), wu64(*caps), m, totals.data_ptr(), scratch.data_ptr(), sb,
         _native.stream_ptr()))
-    if trim:
-        packed = [p[:t] for p, t in zip(packed, totals.tolist())]  # one read-back for all wires
-    return list(zip(packed, offs))
+    return totals
 
 
 def encoded_capacity(n: int, x: int) -> int:
@@ -294,3 +339,314 @@ def records_to_list(packed_host, offsets_host) -> List[bytes]:
     buf = bytes(packed_host.numpy() if hasattr(packed_host, "numpy") else packed_host)
     off = offsets_host.tolist()
     return [buf[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+# ------------------------------------------------------------------ wire frames
+# One wire and its record lengths in one buffer (include/dn_shamir.h, "Share
+# wire frames"):
+#     [magic "DNSHREC1"][n u64][x u64][records_bytes u64][lens u8[n], zero-padded to 16][records]
+FRAME_MAGIC = b"DNSHREC1"
+FRAME_HEADER = 32
+
+
+def _frame_lib():
+    L = _lib()
+    if not hasattr(L, "dn_m521_frame_open"):
+        raise RuntimeError(f"{_native.lib_path()} lacks dn_m521_frame_open: rebuild the native library")
+    return L
+
+
+def frame_records_offset(n: int) -> int:
+    """R(n) = 32 + 16 * ceil(n / 16): where the records of an n-record frame start."""
+    return int(_frame_lib().dn_m521_frame_records_offset(n))
+
+
+def frame_capacity(n: int, x: int) -> int:
+    """Bytes a frame of n records of share x may take: R(n) + encoded_capacity(n, x)."""
+    return int(_frame_lib().dn_m521_frame_capacity(n, x))
+
+
+def _frame_out(t, cap: int, dev, what: str):
+    """A frame buffer: the caller's (>= cap bytes, 16-byte aligned) or a fresh one."""
+    import torch
+
+    t = _out(t, cap, torch.uint8, dev, what)
+    if t.data_ptr() & 15:
+        raise ValueError(f"{what}: the buffer must be 16-byte aligned (the lengths are stored as 16-byte words)")
+    return t
+
+
+def _finish(L, offs, frames, xs, n: int) -> None:
+    m = len(frames)
+    vps = ctypes.c_void_p * m
+    _native.check(L.dn_m521_frame_finish(vps(*[o.data_ptr() for o in offs]), vps(*[f.data_ptr() for f in frames]),
+                                         (ctypes.c_uint64 * m)(*xs), m, n, _native.stream_ptr()))
+
+
+def encode_share_frame(vec, n: int, x: int, *, trim: bool = True, out=None, offsets=None):
+    """Share x of n elements (uint8 device tensor, tiled) -> (frame uint8, offsets int64[n+1]).
+
+    `encode_share_vec` with its output inside a wire frame: the encoder writes
+    the records at frame[R(n):] (R = frame_records_offset; nothing is copied),
+    then one launch writes the lengths, the pad and the header
+    (dn_m521_frame_finish).  The frame is what goes to `aes.encrypt_vec`;
+    frame[R(n):] with `offsets` is a wire as it stands.
+    out / offsets: caller buffers (>= frame_capacity(n, x) bytes, 16-byte
+    aligned; >= n + 1 entries), else allocated.  trim=True cuts the frame to
+    its length R(n) + offsets[n] (one read-back); trim=False returns the
+    full-capacity tensor without synchronising (the length is in the header).
+    Argument errors are raised before any device use."""
+    import torch
+
+    what = "encode_share_frame"
+    n, x = int(n), int(x)
+    if n < 0:
+        raise ValueError(f"{what}: n must not be negative")
+    if not 0 <= x < (1 << 64):
+        raise NotImplementedError(f"{what}: x must fit 64 bits")
+    vb = field.vec_bytes(n)
+    if not (isinstance(vec, torch.Tensor) and vec.dtype == torch.uint8 and vec.is_contiguous() and vec.numel() >= vb):
+        raise ValueError(f"{what}: vec must be a contiguous uint8 tensor of >= {vb} bytes")
+    dev = vec.device
+    for name, t, dtype in (("out", out, torch.uint8), ("offsets", offsets, torch.int64)):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous()
+                                  and t.device == dev):
+            raise ValueError(f"{what} {name}: expected a contiguous {dtype} tensor on {dev}")
+    if dev.type != "cuda":
+        _native.require_device()
+        raise ValueError(f"{what}: vec must be on a HIP device (it is on {dev})")
+    L = _frame_lib()
+    R = int(L.dn_m521_frame_records_offset(n))
+    cap = int(L.dn_m521_encoded_capacity(n, x))
+    frame = _frame_out(out, R + cap, dev, f"{what} out")
+    offsets = _out(offsets, n + 1, torch.int64, dev, f"{what} offsets")[: n + 1]
+    if n:  # every entry is written by the encoder (offsets[n] by the last element)
+        sb = int(L.dn_m521_codec_scratch_bytes(n))
+        scratch = _scratch(dev, sb)
+        _native.check(L.dn_m521_encode_shares(vec.data_ptr(), n, x, offsets.data_ptr(), frame.data_ptr() + R, cap,
+                                              scratch.data_ptr(), sb, _native.stream_ptr()))
+    else:
+        offsets.zero_()
+    _finish(L, [offsets], [frame], [x], n)
+    if trim:
+        frame = frame[: R + int(offsets[n].item())]
+    return frame, offsets
+
+
+def encode_frames_many(blocks, ns: Sequence[int], xs: Optional[Sequence[int]] = None, *,
+                       rows: Optional[Sequence[int]] = None, trim: bool = True, outs=None, offsets=None
+                       ) -> List[Tuple[object, object]]:
+    """`encode_shares_many` into wire frames: for each x one frame holding the
+    records of every tensor back to back and their lengths — three encoder
+    launches for the records (written at frame[R(n_total):], nothing copied)
+    and ONE dn_m521_frame_finish launch for the lengths and headers of all
+    wires.  Arguments and errors are encode_shares_many's, raised before any
+    device use, except:
+    outs     per x a uint8 device tensor of >= frame_capacity(n_total, xs[i])
+             bytes, 16-byte aligned.  Default: allocated
+    trim     True cuts every frame to R(n_total) + its records' bytes with ONE
+             read-back for all wires; False returns the full-capacity tensors
+             without synchronising
+    Returns one (frame, offsets[: n_total + 1]) per x; frame[R(n_total):] with
+    the offsets is the wire encode_shares_many returns.  n_total == 0 gives
+    header-only frames."""
+    import torch
+
+    what = "encode_frames_many"
+    ns, ptrs, pitches, tiles, xs, rows, dev = _many_args(what, blocks, ns, xs, rows, outs, offsets)
+    if not xs:
+        return []
+    n_total = sum(ns)
+    dev = _many_device(what, dev)
+    L = _frame_lib()
+    m = len(xs)
+    R = int(L.dn_m521_frame_records_offset(n_total))
+    caps = [int(L.dn_m521_encoded_capacity(n_total, x)) for x in xs]
+    frames, offs = [], []
+    for i in range(m):
+        frames.append(_frame_out(None if outs is None else outs[i], R + caps[i], dev, f"{what} outs[{i}]"))
+        offs.append(_out(None if offsets is None else offsets[i], n_total + 1, torch.int64, dev,
+                         f"{what} offsets[{i}]")[: n_total + 1])
+    totals = None
+    if n_total:
+        totals = _encode_many(L, ns, ptrs, pitches, tiles, xs, rows, [f[R:] for f in frames], offs, caps, dev)
+    else:
+        for o in offs:
+            o.zero_()
+    _finish(L, offs, frames, xs, n_total)
+    if trim:
+        lens = totals.tolist() if totals is not None else [0] * m  # one read-back for all wires
+        frames = [f[: R + t] for f, t in zip(frames, lens)]
+    return list(zip(frames, offs))
+
+
+def _headers(frames, what: str):
+    """(n, x) of every frame's header: one read-back for all frames."""
+    import torch
+
+    if any(f.numel() < FRAME_HEADER for f in frames):
+        raise ValueError(f"{what}: a frame is shorter than its {FRAME_HEADER}-byte header")
+    host = torch.stack([f[:FRAME_HEADER] for f in frames]).cpu().numpy()
+    words = host.view("<u8")  # [m, 4]: magic, n, x, records_bytes
+    return [(int(w[1]), int(w[2])) for w in words]
+
+
+def open_frames(frames, n: Optional[int], xs: Optional[Sequence[int]], *, offsets=None, bad=None
+                ) -> List[Tuple[object, object]]:
+    """Wire frames -> [(packed, offsets int64[n + 1])], what the record calls
+    (`decode_share_vec`, `resolve_records_vec`, `sum_records_vec`) take: one
+    validated scan of the lengths, batched over all frames of the call (three
+    launches per 64 frames, dn_m521_frame_open).  `packed` is the view
+    frame[R(n):]; nothing is copied.
+
+    frames   sequence of contiguous 1-D uint8 device tensors (one device), each
+             cut to its length — `aes.decrypt_vec`'s result.  A frame that is
+             not 16-byte aligned is copied once, as decode_share_vec copies a
+             misaligned `packed`
+    n        records per frame (all frames of a call share it); None reads it
+             from the headers
+    xs       the abscissa each frame should carry; None reads them from the
+             headers.  Either None costs one read-back for all frames
+    offsets  optional per frame an int64 device tensor of >= n + 1 entries
+    bad      None: one read-back after the launches, ValueError naming both
+             counts if a header is not (magic, n, xs[i], len(frame) - R(n)) or
+             a frame's lengths do not sum to len(frame) - R(n).  An int32
+             device tensor [2]: the two counts are ADDED to it and the call
+             does not synchronise; `check_bad_frames(bad)` raises later
+    Whatever the bytes say, the offsets are monotone and inside `packed`
+    (offsets[e] = min(prefix, len(packed))), so they are safe to hand on.
+    Argument errors are raised before any device use."""
+    import torch
+
+    what = "open_frames"
+    frames = list(frames)
+    if not frames:
+        raise ValueError(f"{what}: no frames")
+    first = frames[0]
+    for f in frames:
+        if not (isinstance(f, torch.Tensor) and f.dtype == torch.uint8 and f.dim() == 1 and f.is_contiguous()):
+            raise ValueError(f"{what}: frames must be contiguous 1-D uint8 tensors")
+        if f.device != first.device:
+            raise ValueError(f"{what}: every frame must be on one device")
+    m = len(frames)
+    if n is not None:
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"{what}: n must not be negative")
+    if xs is not None:
+        xs = [int(x) for x in xs]
+        if len(xs) != m:
+            raise ValueError(f"{what}: {len(xs)} abscissas for {m} frames")
+        if any(not 0 <= x < (1 << 64) for x in xs):
+            raise ValueError(f"{what}: x must fit 64 bits")
+    if offsets is not None:
+        offsets = list(offsets)
+        if len(offsets) != m:
+            raise ValueError(f"{what}: {len(offsets)} offsets for {m} frames")
+        for o in offsets:
+            if not (isinstance(o, torch.Tensor) and o.dtype == torch.int64 and o.dim() == 1 and o.is_contiguous()
+                    and o.device == first.device):
+                raise ValueError(f"{what}: offsets must be contiguous 1-D int64 tensors on the frames' device")
+    if bad is not None and not (isinstance(bad, torch.Tensor) and bad.dtype == torch.int32
+                                and tuple(bad.shape) == (2,) and bad.is_contiguous() and bad.device == first.device):
+        raise ValueError(f"{what}: bad must be a contiguous int32 tensor [2] on the frames' device")
+    L = _frame_lib()
+
+    def sizes(n: int) -> int:
+        """R(n), once every frame and offsets buffer is known to hold n records."""
+        R = int(L.dn_m521_frame_records_offset(n))
+        for i, f in enumerate(frames):
+            if f.numel() < R:
+                raise ValueError(f"{what}: frame {i} has {f.numel()} bytes, fewer than the {R} before its records")
+            if offsets is not None and offsets[i].numel() < n + 1:
+                raise ValueError(f"{what}: offsets must hold n + 1 = {n + 1} entries, got {offsets[i].numel()}")
+        return R
+
+    if n is not None:
+        sizes(n)
+    dev = _native.require_device()
+    if first.device != dev:
+        raise ValueError(f"{what}: frames must be on {dev}")
+    if n is None or xs is None:
+        heads = _headers(frames, what)
+        if n is None:
+            if len({h[0] for h in heads}) != 1:
+                raise ValueError(f"{what}: the frames' headers carry different record counts: {[h[0] for h in heads]}")
+            n = heads[0][0]
+        if xs is None:
+            xs = [h[1] for h in heads]
+    R = sizes(n)
+    # the kernels load 16-byte words: one aligned device copy of a misaligned view
+    frames = [f.clone() if f.data_ptr() & 15 else f for f in frames]
+    offs = [_out(None if offsets is None else offsets[i], n + 1, torch.int64, dev, f"{what} offsets[{i}]")[: n + 1]
+            for i in range(m)]
+    checked = bad is None
+    if checked:
+        bad = torch.zeros(2, dtype=torch.int32, device=dev)
+    sb = int(L.dn_m521_frame_scratch_bytes(n, m))
+    scratch = _scratch(dev, sb)
+    vps, u64s = ctypes.c_void_p * m, ctypes.c_uint64 * m
+    _native.check(L.dn_m521_frame_open(vps(*[f.data_ptr() for f in frames]), u64s(*[f.numel() for f in frames]),
+                                       u64s(*xs), m, n, vps(*[o.data_ptr() for o in offs]), bad.data_ptr(),
+                                       scratch.data_ptr(), sb, _native.stream_ptr()))
+    if checked:
+        check_bad_frames(bad)
+    return [(f[R:], o) for f, o in zip(frames, offs)]
+
+
+def open_frame(frame, n: Optional[int], x: Optional[int], *, offsets=None, bad=None):
+    """`open_frames` for one frame: (packed, offsets)."""
+    return open_frames([frame], n, None if x is None else [x], offsets=None if offsets is None else [offsets],
+                       bad=bad)[0]
+
+
+def check_bad_frames(bad) -> None:
+    """Raise if a deferred `open_frames(..., bad=flag)` met frames whose header
+    is not what the caller expects (flag[0]) or whose lengths do not sum to
+    their records' bytes (flag[1]): one read-back of the two counts."""
+    nhead, nsum = (int(c) for c in bad.tolist())
+    if nhead or nsum:
+        raise ValueError(f"open_frames: {nhead} frames whose header is not (magic, n, x, records_bytes), "
+                         f"{nsum} frames whose lengths do not sum to their records' bytes")
+
+
+class FrameFields(NamedTuple):
+    n: int
+    x: int
+    records_bytes: int
+    lens: object  # numpy uint8[n]
+    records: object  # numpy uint8[records_bytes]
+
+
+def frame_fields_host(buf, n: Optional[int] = None, x: Optional[int] = None) -> FrameFields:
+    """A host copy of a frame (bytes, numpy uint8 or a CPU tensor) parsed with
+    numpy alone — for peers without a GPU and for tests.  Raises ValueError on
+    the faults the device counts: a wrong magic, a record count or abscissa
+    other than the expected `n` / `x` (where given), a records_bytes that is
+    not len(buf) - R(n), lengths that do not sum to it."""
+    import numpy as np
+
+    what = "frame_fields_host"
+    if hasattr(buf, "numpy"):
+        buf = buf.numpy()
+    a = np.frombuffer(bytes(buf), dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) \
+        else np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+    if a.size < FRAME_HEADER:
+        raise ValueError(f"{what}: {a.size} bytes, fewer than the {FRAME_HEADER}-byte header")
+    if a[:8].tobytes() != FRAME_MAGIC:
+        raise ValueError(f"{what}: wrong magic {a[:8].tobytes()!r}")
+    hn, hx, hbytes = (int(v) for v in a[8:FRAME_HEADER].view("<u8"))
+    if n is not None and hn != n:
+        raise ValueError(f"{what}: the header carries n = {hn}, expected {n}")
+    if x is not None and hx != x:
+        raise ValueError(f"{what}: the header carries x = {hx}, expected {x}")
+    R = FRAME_HEADER + ((hn + 15) & ~15)
+    if a.size < R:
+        raise ValueError(f"{what}: {a.size} bytes, fewer than the {R} before the records of n = {hn}")
+    if hbytes != a.size - R:
+        raise ValueError(f"{what}: the header carries records_bytes = {hbytes}, the buffer holds {a.size - R}")
+    lens = a[FRAME_HEADER:FRAME_HEADER + hn]
+    total = int(lens.sum(dtype=np.uint64))
+    if total != hbytes:
+        raise ValueError(f"{what}: the lengths sum to {total}, not records_bytes = {hbytes}")
+    return FrameFields(hn, hx, hbytes, lens, a[R:])

@@ -601,6 +601,78 @@ int dn_m521_sum_records(const uint8_t* const* in, const uint64_t* in_bytes, cons
                         uint64_t m, uint64_t x, const uint8_t* negate, const void* acc, void* out,
                         uint32_t* bad_counts /* device uint32[2] */, uint64_t n_elem, void* stream);
 
+/*
+ * Share wire frames: one wire and its record lengths in one buffer.  The
+ * record calls above speak (packed, offsets[n_elem + 1]); a record
+ * ([len(xb)][xb][yb], shamir.py:28-45) carries no length for yb, so a receiver
+ * needs the offsets as well as the bytes.  A frame (version 1, little-endian)
+ * carries them as u8 lengths in front of the records:
+ *     bytes  0.. 7   magic "DNSHREC1"
+ *     bytes  8..15   n              u64   records in the frame
+ *     bytes 16..23   x              u64   the wire's abscissa
+ *     bytes 24..31   records_bytes  u64   = offsets[n]
+ *     bytes 32..     lens           u8[n], lens[e] = offsets[e + 1] - offsets[e]
+ *                                   (at most 1 + 8 + 66 = 75), zero-padded to a
+ *                                   multiple of 16
+ *     bytes R(n)..   the records, records_bytes of them: exactly `packed`
+ *     R(n) = 32 + 16 * ceil(n / 16)        (dn_m521_frame_records_offset)
+ *     frame_bytes = R(n) + records_bytes;  capacity = R(n) +
+ *     dn_m521_encoded_capacity(n, x)       (dn_m521_frame_capacity)
+ * Every position depends on n alone, and R(n) is a multiple of 16: in a
+ * 16-byte aligned frame the records take the encoder's and the consumers' wide
+ * paths.  The sender encodes with `out` = frame + R(n) (dn_m521_encode_shares,
+ * or dn_m521_encode_shares_many for a list) and then calls
+ * dn_m521_frame_finish; frame + R(n) with the same offsets stays a wire as it
+ * stands.  No reference counterpart: the reference sends one HTTP part per
+ * share (shamir.py:28-45 per element).
+ *
+ * dn_m521_frame_finish (shamir.py:28-45): for each of the m wires, offsets ->
+ * lens, the zero pad and the 32-byte header, records_bytes = offsets[n_elem]
+ * read on the device.  One launch per DN_M521_FRAME_GROUP wires (the wire
+ * descriptors travel in the kernel arguments).
+ *   offsets, frames, xs  HOST arrays of m entries: offsets[i] DEVICE
+ *                 uint64[n_elem + 1], 8-byte aligned (not read when n_elem ==
+ *                 0); frames[i] DEVICE, 16-byte aligned, at least R(n_elem)
+ *                 bytes; xs[i] the abscissa written to the header
+ * Bytes [0, R(n_elem)) of every frame are written, nothing else.  n_elem == 0
+ * is DN_OK: a header-only frame, still written.
+ *
+ * dn_m521_frame_open (shamir.py:36-45 needs each record's extent): for each of
+ * the m frames, all of n_elem records, lens -> offsets_out[i][0 .. n_elem] as
+ * an exclusive prefix in 64 bits.  Three launches per DN_M521_FRAME_GROUP
+ * frames: per-workgroup totals, one scan of the totals per frame, expansion.
+ * Frames come off the wire, so
+ *     offsets_out[i][e] = min(lens[0] + ... + lens[e - 1], frame_bytes[i] - R(n_elem)):
+ * whatever the bytes say, the offsets are monotone and lie inside the view
+ * frame + R(n_elem) of frame_bytes[i] - R(n_elem) bytes (the clamp uses the
+ * caller's size, never the header).  Pad bytes are not trusted to be zero.
+ *   frames, frame_bytes, xs, offsets_out  HOST arrays of m entries: frames[i]
+ *                 DEVICE, 16-byte aligned, frame_bytes[i] >= R(n_elem) bytes;
+ *                 xs[i] the abscissa frame i should carry; offsets_out[i]
+ *                 DEVICE uint64[n_elem + 1], 8-byte aligned
+ *   bad_counts    DEVICE uint32[2], ADDED to, once per frame: [0] a header that
+ *                 is not (magic, n_elem, xs[i], frame_bytes[i] - R(n_elem)),
+ *                 [1] lengths that do not sum to frame_bytes[i] - R(n_elem)
+ *   scratch       DEVICE, 8-byte aligned, dn_m521_frame_scratch_bytes(n_elem,
+ *                 m) bytes: 8 per (frame, 4096 elements)
+ * n_elem == 0 gives offsets_out[i][0] = 0.
+ *
+ * Both: DN_ERR_ARG, before any device call: m == 0, a null pointer (the wire
+ * named where one is at fault), a frame that is not 16-byte aligned, offsets
+ * that are not 8-byte aligned, frame_bytes[i] < R(n_elem), a scratch too small,
+ * ceil(n_elem / 256) >= 2^31.  Neither synchronises `stream`; both can be
+ * captured into a graph.
+ */
+#define DN_M521_FRAME_GROUP 64
+uint64_t dn_m521_frame_records_offset(uint64_t n_elem);
+uint64_t dn_m521_frame_capacity(uint64_t n_elem, uint64_t x);
+int dn_m521_frame_finish(const uint64_t* const* offsets, uint8_t* const* frames, const uint64_t* xs, uint64_t m,
+                         uint64_t n_elem, void* stream);
+uint64_t dn_m521_frame_scratch_bytes(uint64_t n_elem, uint64_t m);
+int dn_m521_frame_open(const uint8_t* const* frames, const uint64_t* frame_bytes, const uint64_t* xs, uint64_t m,
+                       uint64_t n_elem, uint64_t* const* offsets_out, uint32_t* bad_counts /* device uint32[2] */,
+                       void* scratch, uint64_t scratch_bytes, void* stream);
+
 /* Thread-local message of the last failure (never NULL). */
 const char* dn_last_error(void);
 
