@@ -13,11 +13,11 @@
 //       records_bytes = offsets[n] included, all on the device.
 //   dn_m521_frame_open     three launches for all frames of a call: per-block
 //       totals of the lengths (a thread's 16 lengths are one 16-byte load,
-//       summed by four v_sad_u8), one scan of the block totals per frame (the
-//       block-total scan of codec_m521.hip, restated: that file is not
-//       touched), and the expansion into int64 offsets, which meets the
-//       element-interleaved store order in LDS so that every wave-level store
-//       covers 512 contiguous bytes.  No workgroup waits on another.
+//       summed by four v_sad_u8), one scan of the block totals per frame
+//       (wire_emit.hpp, the encoders' scan), and the expansion into int64
+//       offsets, which meets the element-interleaved store order in LDS so
+//       that every wave-level store covers 512 contiguous bytes.  No workgroup
+//       waits on another.
 //
 // The frame is the second grid dimension; the per-frame descriptors travel in
 // the kernel arguments (up to DN_M521_FRAME_GROUP frames a launch; the entry
@@ -29,6 +29,7 @@
 
 #include "dn_internal.hpp"
 #include "frame_plan.hpp"
+#include "wire_emit.hpp"
 
 namespace dn {
 namespace fr {
@@ -168,58 +169,11 @@ __global__ void __launch_bounds__(kFrameBlock) frame_totals_kernel(const OpenArg
 }
 
 // Open, launch 2: exclusive scan of a frame's block totals in one workgroup
-// (scan_blocks_kernel of codec_m521.hip, restated with the frame as
-// blockIdx.y): the totals are staged in LDS as 32-bit words with coalesced
-// loads, each thread scans a contiguous run of them (padded rows: no bank
-// conflicts), the run sums are scanned across threads in 64 bits.  The grand
-// total is compared with the size of the `packed` view.
-__global__ void __launch_bounds__(kFrameScanThreads) frame_scan_kernel(const OpenArgs a) {
-  __shared__ uint32_t s[kFrameScanStage + kFrameScanStage / kFrameScanRun];  // row of 8 + 1 pad per thread
-  __shared__ uint64_t s_w[kFrameScanThreads / 64];
-  const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-  const uint64_t nb = a.nb;
-  uint64_t* tot = a.tot + blockIdx.y * nb;
-  uint64_t carry = 0;  // total of the previous passes
-  const uint64_t passes = frame_scan_passes(nb);
-  for (uint64_t p = 0; p < passes; ++p) {
-    const uint64_t base = p * kFrameScanStage;
-    const uint32_t m = frame_scan_count(nb, p);
-    for (uint32_t i = t; i < m; i += kFrameScanThreads) s[i + i / kFrameScanRun] = static_cast<uint32_t>(tot[base + i]);
-    __syncthreads();
-    uint64_t sum = 0;
-#pragma unroll
-    for (uint32_t j = 0; j < kFrameScanRun; ++j) {
-      const uint32_t i = kFrameScanRun * t + j;
-      sum += i < m ? s[i + i / kFrameScanRun] : 0u;
-    }
-    uint64_t inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t v = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += v;
-    }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    uint64_t wbase = 0, ptot = 0;
-#pragma unroll
-    for (int i = 0; i < static_cast<int>(kFrameScanThreads / 64); ++i) {
-      wbase += (i < static_cast<int>(wv)) ? s_w[i] : 0u;
-      ptot += s_w[i];
-    }
-    uint64_t run = carry + wbase + inc - sum;
-#pragma unroll
-    for (uint32_t j = 0; j < kFrameScanRun; ++j) {
-      const uint32_t i = kFrameScanRun * t + j;
-      if (i < m) {
-        const uint32_t v = s[i + i / kFrameScanRun];
-        tot[base + i] = run;
-        run += v;
-      }
-    }
-    carry += ptot;
-    __syncthreads();
-  }
-  if (t == 0 && carry != a.w[blockIdx.y].rec_bytes) atomicAdd(a.bad + 1, 1u);
+// (the frame is blockIdx.y).  The grand total is compared with the size of
+// the `packed` view.
+__global__ void __launch_bounds__(kScanThreads) frame_scan_kernel(const OpenArgs a) {
+  const uint64_t total = scan_block_totals(a.tot + blockIdx.y * a.nb, a.nb);
+  if (threadIdx.x == 0 && total != a.w[blockIdx.y].rec_bytes) atomicAdd(a.bad + 1, 1u);
 }
 
 // Open, launch 3: the lengths again, their exclusive prefix inside the
@@ -357,7 +311,7 @@ extern "C" int dn_m521_frame_open(const uint8_t* const* frames, const uint64_t* 
     a.tot = static_cast<uint64_t*>(scratch) + first * nb;  // every frame of the call has its own totals
     a.bad = bad_counts;
     hipLaunchKernelGGL(fr::frame_totals_kernel, dim3(gx, k), dim3(kFrameBlock), 0, s, a);
-    hipLaunchKernelGGL(fr::frame_scan_kernel, dim3(1, k), dim3(kFrameScanThreads), 0, s, a);
+    hipLaunchKernelGGL(fr::frame_scan_kernel, dim3(1, k), dim3(kScanThreads), 0, s, a);
     hipLaunchKernelGGL(fr::frame_expand_kernel, dim3(gx, k), dim3(kFrameBlock), 0, s, a);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return set_error(DN_ERR_HIP, "%s: %s", name, hipGetErrorString(err));

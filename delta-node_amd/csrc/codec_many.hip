@@ -22,7 +22,7 @@
 //       lengths the encoder has anyway (wave scan, then across the 4 waves),
 //       offsets[] at the global element index, records laid out in LDS at
 //       their final byte positions and written as aligned chunks plus head /
-//       tail bytes (codec_m521.hip encode_kernel's layout and stores).
+//       tail bytes (wire_emit.hpp: encode_kernel's layout and stores).
 // No per-element prefix array: scratch is 8 bytes per (tile, wire).
 #include <hip/hip_runtime.h>
 
@@ -31,18 +31,17 @@
 #include "dn_internal.hpp"
 #include "enc_plan.hpp"
 #include "m521_device.hpp"
+#include "wire_emit.hpp"
 
 namespace dn {
 namespace em {
 
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / 64;
-constexpr int kMaxRecord = 1 + 8 + 66;  // [len][x up to 8 bytes][y up to 66 bytes]
 constexpr int kGroup = 16;              // wires per launch group
 static_assert(kBlock == static_cast<int>(kSegTile) && kTile == static_cast<int>(kSegTile), "one thread per tile word");
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(4))) EncSegEnt* EncTab;  // read by scalar loads
 
 struct Wire {
@@ -63,19 +62,6 @@ struct Args {
   Wire wire[kGroup];
 };
 static_assert(sizeof(Args) <= 4096, "the kernel arguments must fit the 4 KB kernarg segment");
-
-// Bytes of the minimal big-endian form of a non-zero 32-bit limb.
-__device__ __forceinline__ uint32_t limb_bytes(uint32_t l) { return (32u - __builtin_clz(l) + 7u) / 8u; }
-
-// Minimal big-endian byte length of a canonical 17-limb value (0 -> 0).
-__device__ __forceinline__ uint32_t y_len(const uint32_t v[kLimbs]) {
-  uint32_t len = 0;
-#pragma unroll
-  for (int i = 0; i < kLimbs; ++i) {
-    if (v[i]) len = 4u * i + limb_bytes(v[i]);
-  }
-  return len;
-}
 
 // y length of word w of a tile from limbs 15 .. 0 (the top limb was zero).
 // (Inlined: a call would hand the descriptor over in VGPRs.)
@@ -119,68 +105,12 @@ __global__ void __launch_bounds__(kBlock) tile_totals_kernel(Args a) {
   if (lane == 0) a.tile_tot[static_cast<uint64_t>(i) * a.ntiles + g] = sum;
 }
 
-// (2) Exclusive scan of one wire's tile totals in one workgroup
-// (codec_m521.hip scan_blocks_kernel's method): the totals are staged in LDS
-// as 32-bit words (a tile's total is at most 256 * 75 bytes) with coalesced
-// loads, each thread scans a contiguous run of them (padded rows: no bank
-// conflicts), the run sums are scanned across threads.
-constexpr int kScanThreads = 1024;
-constexpr int kScanStage = 8192;  // totals staged per pass (34 KB of LDS)
-
+// (2) Exclusive scan of one wire's tile totals in one workgroup, and the
+// wire's length (a tile's total is at most 256 * 75 bytes).
 __global__ void __launch_bounds__(kScanThreads) scan_tiles_kernel(uint64_t* __restrict__ tile_tot, uint32_t ntiles,
                                                                   uint64_t* __restrict__ totals) {
-  __shared__ uint32_t s[kScanStage + kScanStage / 8];  // row of 8 + 1 pad per thread
-  __shared__ uint64_t s_w[kScanThreads / 64];
-  uint64_t* tot = tile_tot + static_cast<uint64_t>(blockIdx.x) * ntiles;
-  const uint64_t nb = ntiles;
-  const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-  uint64_t carry = 0;  // total of the previous passes
-  for (uint64_t base = 0; base < nb; base += kScanStage) {
-    const uint32_t m = static_cast<uint32_t>(nb - base < kScanStage ? nb - base : kScanStage);
-    for (uint32_t i = t; i < m; i += kScanThreads) s[i + i / 8] = static_cast<uint32_t>(tot[base + i]);
-    __syncthreads();
-    // thread t: totals 8 t .. 8 t + 7 of this pass
-    uint64_t sum = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t i = 8u * t + j;
-      sum += i < m ? s[i + i / 8] : 0u;
-    }
-    uint64_t inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t v = __shfl_up(inc, d);
-      if (lane >= static_cast<uint32_t>(d)) inc += v;
-    }
-    if (lane == 63) s_w[wv] = inc;
-    __syncthreads();
-    uint64_t wbase = 0, ptot = 0;
-#pragma unroll
-    for (int w = 0; w < kScanThreads / 64; ++w) {
-      wbase += (w < static_cast<int>(wv)) ? s_w[w] : 0u;
-      ptot += s_w[w];
-    }
-    uint64_t run = carry + wbase + inc - sum;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const uint32_t i = 8u * t + j;
-      if (i < m) {
-        const uint32_t v = s[i + i / 8];
-        tot[base + i] = run;
-        run += v;
-      }
-    }
-    carry += ptot;
-    __syncthreads();
-  }
-  if (t == 0) totals[blockIdx.x] = carry;
-}
-
-__device__ __forceinline__ void lds_put_bytes(uint8_t* sb, int32_t lo, int32_t hi, int32_t pos, uint32_t word) {
-  // bytes of `word` (LE at LDS position pos) that fall inside [lo, hi)
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (pos + i >= lo && pos + i < hi) sb[pos + i] = static_cast<uint8_t>(word >> (8 * i));
+  const uint64_t total = scan_block_totals(tile_tot + static_cast<uint64_t>(blockIdx.x) * ntiles, ntiles);
+  if (threadIdx.x == 0) totals[blockIdx.x] = total;
 }
 
 // (3) One workgroup per (global tile, wire), thread = word of the tile; one
@@ -194,8 +124,7 @@ __device__ __forceinline__ void lds_put_bytes(uint8_t* sb, int32_t lo, int32_t h
 // the tile is a tensor's partial last one and the next tensor's first record
 // follows inside the same dword — is never touched.
 __global__ void __launch_bounds__(kBlock) encode_many_kernel(Args a) {
-  constexpr int kRowWords = ((64 * kMaxRecord + 8 + 16) / 4 + 2 + 3) & ~3;  // 16-B aligned rows
-  __shared__ __attribute__((aligned(16))) uint32_t s_buf[kWaves][kRowWords];
+  __shared__ __attribute__((aligned(16))) uint32_t s_buf[kWaves][kEncRowWords];
   __shared__ uint32_t s_w[kWaves];
   const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
   const uint32_t g = blockIdx.x, i = blockIdx.y;
@@ -241,57 +170,13 @@ __global__ void __launch_bounds__(kBlock) encode_many_kernel(Args a) {
   const uint64_t B = __shfl(endl, last);
   const uint64_t A4 = w16 ? (A & ~15ull) : (A & ~3ull);  // LDS byte 0 of the window
   uint8_t* sb = reinterpret_cast<uint8_t*>(s_buf[wv]);
-  uint32_t* sw4 = s_buf[wv];
   if (valid) {
     const int32_t p = static_cast<int32_t>(off - A4);
-    const int32_t ys = p + 1 + static_cast<int32_t>(xlen);
-    const int32_t E = ys + static_cast<int32_t>(ylen);
     sb[p] = static_cast<uint8_t>(xlen);
     for (uint32_t j = 0; j < xlen; ++j) sb[p + 1 + j] = static_cast<uint8_t>(xbe >> (8u * j));
-    if (ylen) {
-      uint32_t W[kLimbs + 1];
-#pragma unroll
-      for (int m = 0; m < kLimbs; ++m) W[m] = __builtin_bswap32(v[kLimbs - 1 - m]);
-      W[kLimbs] = 0u;
-      const int32_t base = E - 4 * kLimbs;           // LDS position of image byte 0
-      const uint32_t rr = static_cast<uint32_t>(-base) & 3u;
-      const int32_t d0 = (base + static_cast<int32_t>(rr)) >> 2;  // dword holding image bytes rr..rr+3
-      // dword d0 - 1: image bytes 0..rr-1 at its top (rr > 0)
-      if (rr) lds_put_bytes(sb, ys, E, 4 * (d0 - 1), __builtin_amdgcn_alignbyte(W[0], 0u, rr));
-#pragma unroll
-      for (int m = 0; m < kLimbs; ++m) {
-        const uint32_t u = __builtin_amdgcn_alignbyte(W[m + 1], W[m], rr);
-        const int32_t pos = 4 * (d0 + m);
-        if (pos >= ys && pos + 4 <= E) sw4[d0 + m] = u;
-        else if (pos + 4 > ys && pos < E) lds_put_bytes(sb, ys, E, pos, u);
-      }
-    }
+    if (ylen) lay_y(s_buf[wv], p + 1 + static_cast<int32_t>(xlen), static_cast<int32_t>(ylen), v);
   }
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  // head bytes [A, a4), aligned body [a4, b4), tail [b4, B)
-  const uint64_t al = w16 ? 16u : 4u;
-  const uint64_t a4 = (A + al - 1) & ~(al - 1), b4 = B & ~(al - 1);
-  if (a4 > b4) {  // the whole range sits inside one aligned chunk
-    for (uint64_t q = A + lane; q < B; q += 64) out[q] = sb[q - A4];
-    return;
-  }
-  if (lane < a4 - A) out[A + lane] = sb[A + lane - A4];
-  if (lane < B - b4) out[b4 + lane] = sb[b4 + lane - A4];
-  if (w16) {
-    const u32x4* sq = reinterpret_cast<const u32x4*>(s_buf[wv]);
-    u32x4* oq = reinterpret_cast<u32x4*>(out + a4);
-    const uint32_t base_q = static_cast<uint32_t>((a4 - A4) / 16);
-    const uint32_t nq = static_cast<uint32_t>((b4 - a4) / 16);
-    for (uint32_t q = lane; q < nq; q += 64) __builtin_nontemporal_store(sq[base_q + q], oq + q);
-  } else {
-    const uint32_t* sw = s_buf[wv];
-    uint32_t* ow = reinterpret_cast<uint32_t*>(out + a4);
-    const uint32_t base_w = static_cast<uint32_t>((a4 - A4) / 4);
-    const uint32_t nw = static_cast<uint32_t>((b4 - a4) / 4);
-    for (uint32_t q = lane; q < nw; q += 64) __builtin_nontemporal_store(sw[base_w + q], ow + q);
-  }
+  flush_window(s_buf[wv], out, A, B, A4, w16, lane);
 }
 
 constexpr uint64_t table_bytes(uint64_t nseg) { return ((nseg + 1) * sizeof(EncSegEnt) + 15u) & ~15ull; }
@@ -392,7 +277,7 @@ extern "C" int dn_m521_encode_shares_many(const uint64_t* n_elem, const void* co
     const uint32_t nt = a.ntiles;
     hipLaunchKernelGGL(em::tile_totals_kernel, dim3((nt + em::kWaves - 1) / em::kWaves, a.nw), dim3(em::kBlock), 0, st,
                        a);
-    hipLaunchKernelGGL(em::scan_tiles_kernel, dim3(a.nw), dim3(em::kScanThreads), 0, st, a.tile_tot, nt, a.totals);
+    hipLaunchKernelGGL(em::scan_tiles_kernel, dim3(a.nw), dim3(kScanThreads), 0, st, a.tile_tot, nt, a.totals);
     hipLaunchKernelGGL(em::encode_many_kernel, dim3(nt, a.nw), dim3(em::kBlock), 0, st, a);
   }
   const hipError_t err = hipGetLastError();

@@ -26,6 +26,8 @@
 
 #include <stdint.h>
 
+#include "wire_geom.hpp"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define DN_FRAME_HD __host__ __device__ constexpr
 #else
@@ -36,18 +38,20 @@ namespace dn {
 
 constexpr uint64_t kFrameMagic = 0x3143455248534E44ull;  // "DNSHREC1" read as a little-endian u64
 constexpr uint32_t kFrameHeader = 32;                    // bytes before the lengths
-constexpr int kFrameMaxRecord = 1 + 8 + 66;              // the encoder's longest record (codec_m521.hip kMaxRecord)
-static_assert(kFrameMaxRecord <= 255, "a u8 holds every record length");
+// (a u8 holds every record length: wire_geom.hpp kMaxRecord)
 
 constexpr uint32_t kFrameBlock = 256;                        // threads per workgroup
 constexpr uint32_t kFrameWord = 16;                          // lengths per thread: one 16-byte word
 constexpr uint32_t kFrameElems = kFrameBlock * kFrameWord;   // B: elements per workgroup (4096)
-// the scan of the block totals (scan_blocks_kernel of codec_m521.hip, restated)
-constexpr uint32_t kFrameScanThreads = 1024;
-constexpr uint32_t kFrameScanRun = 8;                                    // totals per thread and pass
-constexpr uint32_t kFrameScanStage = kFrameScanThreads * kFrameScanRun;  // totals per pass (8192)
 // a block's total (<= 4096 * 255) and every in-block prefix fit 32 bits
 static_assert(static_cast<uint64_t>(kFrameElems) * 255u < (1ull << 32), "in-block sums are 32-bit");
+// The scan of the block totals is wire_geom.hpp's.  Its shape under the frame
+// names, for the host replay and for the frame tests, which build their edge
+// lists from the two literals below as they read them in this file.
+constexpr uint32_t kFrameScanThreads = 1024;
+constexpr uint32_t kFrameScanRun = 8;  // totals per thread and pass
+constexpr uint32_t kFrameScanStage = kScanStage;
+static_assert(kFrameScanThreads == kScanThreads && kFrameScanRun == kScanRun, "the frame names follow the scan");
 
 DN_FRAME_HD uint64_t frame_pad16(uint64_t n) { return (n + 15u) & ~15ull; }
 // R(n): where the records start
@@ -105,12 +109,9 @@ DN_FRAME_HD bool frame_open_store(uint64_t n, uint64_t b, uint32_t t, uint32_t j
 }
 
 // Open, launch 2: pass p takes the block totals [p * kFrameScanStage, ...) of
-// a frame, *count of them; thread t scans totals kFrameScanRun * t + j of the
-// pass.
-DN_FRAME_HD uint64_t frame_scan_passes(uint64_t nb) { return (nb + kFrameScanStage - 1u) / kFrameScanStage; }
-DN_FRAME_HD uint32_t frame_scan_count(uint64_t nb, uint64_t p) {
-  const uint64_t left = nb - p * kFrameScanStage;
-  return left < kFrameScanStage ? static_cast<uint32_t>(left) : kFrameScanStage;
-}
+// a frame, frame_scan_count of them; thread t scans totals kFrameScanRun * t + j
+// of the pass (wire_geom.hpp's arithmetic, which the kernel uses).
+DN_FRAME_HD uint64_t frame_scan_passes(uint64_t nb) { return scan_passes(nb); }
+DN_FRAME_HD uint32_t frame_scan_count(uint64_t nb, uint64_t p) { return scan_count(nb, p); }
 
 }  // namespace dn

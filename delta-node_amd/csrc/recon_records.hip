@@ -3,48 +3,34 @@
 // shamir.py:28-33 in, the secrets of `resolve_shares` (shamir.py:68-90) out, in
 // one launch and without the k intermediate tiled vectors.
 //
-// Per element e and wire i the kernel parses record e of wire i exactly as
-// decode_kernel (codec_m521.hip) does — the same window staged in LDS with the
-// same padding and clamps, the same byte-serial path for a window beyond the
-// LDS slice, the same treatment of untrusted offsets — reduces y, negates it
-// where the weight is negative, accumulates |a_i| * y (mac_wide) and, after the
-// last wire, finishes exactly as recon_finish (shamir_m521.hip) does.  The
-// parse and the finish are copies of those two: neither
-// codec_m521.hip nor shamir_m521.hip is touched, so their kernels keep their
-// instructions.  There is no arithmetic of its own here: every primitive is
-// m521_device.hpp's.
+// Per element e and wire i the kernel parses record e of wire i with the
+// functions decode_kernel (codec_m521.hip) parses with (wire_parse.hpp: the
+// window staged in LDS, the byte-serial path for a window beyond the LDS
+// slice, the treatment of untrusted offsets), reduces y, negates it where the
+// weight is negative, accumulates |a_i| * y (mac_wide) and, after the last
+// wire, finishes as recon_finish (shamir_m521.hip) does.  The finish is a copy
+// of that one with a different INV = 1 product.  There is no
+// arithmetic of its own here: every primitive is m521_device.hpp's.
 //
 // One wave = 64 consecutive elements (decode_kernel's unit), one workgroup =
-// one 256-element output tile, one LDS slice per wave, reused wire after wire.
-// A wire's whole window is loaded into registers (at most 5 16-byte or 19
-// 4-byte loads per lane, all issued before the first LDS store) and then
-// stored to LDS.  Loading wire i + 1 under wire i's arithmetic, and staging
-// with decode_kernel's own loop, were measured and did not pay (StageMode
-// below).
+// one 256-element output tile, one LDS slice per wave, reused wire after wire
+// (the wire loop below).  A wire's whole window is loaded into registers (at most 5
+// 16-byte or 19 4-byte loads per lane, all issued before the first LDS store)
+// and then stored to LDS: kSerial.  Loading wire i + 1 under wire i's
+// arithmetic (kAhead) was no faster at k = 3 and k = 5, and decode_kernel's
+// staging loop (kDirect) 20-30 % slower; both are A/B only.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "dn_internal.hpp"
 #include "m521_device.hpp"
+#include "wire_parse.hpp"
 
 namespace dn {
 namespace rr {
 
 constexpr int kBlock = 256;
-// decode_kernel's window geometry (codec_m521.hip), restated
-constexpr int kMaxRecord = 1 + 8 + 66;  // [len][x up to 8 bytes][y up to 66 bytes]
-constexpr int kDecPad = 16;             // LDS bytes before / after each wave's window
-constexpr int kDecWindow = 64 * kMaxRecord + 8;
-constexpr int kWinLimit = kDecWindow + 12;  // Bend - A4 at most this on the LDS path
-constexpr int kRowWords = ((kDecWindow + 16 + 2 * kDecPad) / 4 + 3) & ~3;  // 16-B aligned rows
-// loads per lane that cover the largest LDS-path window
-constexpr int kStageQ = (kWinLimit / 16 + 63) / 64;  // 16-B loads (wide path)
-constexpr int kStageW = (kWinLimit / 4 + 63) / 64;   // 4-B loads (narrow path)
-constexpr int kStageRegs = 4 * kStageQ > kStageW ? 4 * kStageQ : kStageW;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) uint64_t* OffTab;  // read by scalar loads: no kernel writes offsets
 
 struct Wire {
   const uint8_t* in;        // packed records
@@ -71,178 +57,6 @@ struct Args {
   uint32_t w[kLimbs];
 };
 static_assert(sizeof(Args) <= 4096, "the kernel arguments must fit the 4 KB kernarg segment");
-
-// A wave's window of one wire (wave-uniform): records e0 .. eN - 1 are bytes
-// [A, Bend), LDS byte 0 is A4, and `lds` is decode_kernel's condition for the
-// LDS path (else every lane parses its record from global memory).
-struct Win {
-  uint64_t A, Bend, A4;
-  bool lds;
-};
-
-__device__ __forceinline__ Win win_of(const Wire& w, bool w16, uint64_t e0, uint64_t eN) {
-  const OffTab off = (OffTab)w.offsets;
-  Win r;
-  r.A = off[e0];
-  r.Bend = off[eN];
-  r.A4 = w16 ? (r.A & ~15ull) : (r.A & ~3ull);
-  r.lds = r.Bend >= r.A && r.Bend <= w.in_bytes && r.Bend - r.A4 <= static_cast<uint64_t>(kWinLimit);
-  return r;
-}
-
-// A window on its way to LDS: decode_kernel's staging loop cut in two, the
-// loads here and the LDS stores in stage_store (same addresses, same bytes).
-struct Stage {
-  uint32_t r[kStageRegs];
-  uint32_t tail;
-};
-
-__device__ __forceinline__ void stage_load(Stage& s, const uint8_t* __restrict__ in, const Win& w, bool w16,
-                                           uint32_t lane) {
-  if (w16) {
-    const uint64_t B16 = w.Bend & ~15ull;
-    const uint32_t nq = static_cast<uint32_t>((B16 - w.A4) / 16);
-    const u32x4* inq = reinterpret_cast<const u32x4*>(in + w.A4);
-#pragma unroll
-    for (int j = 0; j < kStageQ; ++j) {
-      const uint32_t q = lane + 64u * j;
-      if (q < nq) {
-        const u32x4 t = __builtin_nontemporal_load(inq + q);
-        s.r[4 * j] = t.x;
-        s.r[4 * j + 1] = t.y;
-        s.r[4 * j + 2] = t.z;
-        s.r[4 * j + 3] = t.w;
-      }
-    }
-    if (lane < w.Bend - B16) s.tail = in[B16 + lane];
-  } else {
-    const uint64_t B4 = w.Bend & ~3ull;
-    const uint32_t nw = static_cast<uint32_t>((B4 - w.A4) / 4);
-    const uint32_t* inw = reinterpret_cast<const uint32_t*>(in + w.A4);
-#pragma unroll
-    for (int j = 0; j < kStageW; ++j) {
-      const uint32_t q = lane + 64u * j;
-      if (q < nw) s.r[j] = __builtin_nontemporal_load(inw + q);
-    }
-    if (lane < w.Bend - B4) s.tail = in[B4 + lane];
-  }
-}
-
-__device__ __forceinline__ void stage_store(const Stage& s, uint32_t* S, const Win& w, bool w16, uint32_t lane) {
-  uint8_t* sb = reinterpret_cast<uint8_t*>(S);
-  if (w16) {
-    const uint64_t B16 = w.Bend & ~15ull;
-    const uint32_t nq = static_cast<uint32_t>((B16 - w.A4) / 16);
-    u32x4* Sq = reinterpret_cast<u32x4*>(S);
-#pragma unroll
-    for (int j = 0; j < kStageQ; ++j) {
-      const uint32_t q = lane + 64u * j;
-      if (q < nq) {
-        u32x4 t;
-        t.x = s.r[4 * j];
-        t.y = s.r[4 * j + 1];
-        t.z = s.r[4 * j + 2];
-        t.w = s.r[4 * j + 3];
-        Sq[q] = t;
-      }
-    }
-    if (lane < w.Bend - B16) sb[B16 - w.A4 + lane] = static_cast<uint8_t>(s.tail);
-  } else {
-    const uint64_t B4 = w.Bend & ~3ull;
-    const uint32_t nw = static_cast<uint32_t>((B4 - w.A4) / 4);
-#pragma unroll
-    for (int j = 0; j < kStageW; ++j) {
-      const uint32_t q = lane + 64u * j;
-      if (q < nw) S[q] = s.r[j];
-    }
-    if (lane < w.Bend - B4) sb[B4 - w.A4 + lane] = static_cast<uint8_t>(s.tail);
-  }
-}
-
-// decode_kernel's staging loop as it stands there: global -> registers -> LDS
-// inside one loop (the form without load-ahead).
-__device__ __forceinline__ void stage_direct(uint32_t* S, const uint8_t* __restrict__ in, const Win& w, bool w16,
-                                             uint32_t lane) {
-  uint8_t* sb = reinterpret_cast<uint8_t*>(S);
-  if (w16) {
-    const uint64_t B16 = w.Bend & ~15ull;
-    const uint32_t nq = static_cast<uint32_t>((B16 - w.A4) / 16);
-    const u32x4* inq = reinterpret_cast<const u32x4*>(in + w.A4);
-    u32x4* Sq = reinterpret_cast<u32x4*>(S);
-    for (uint32_t q = lane; q < nq; q += 64) Sq[q] = __builtin_nontemporal_load(inq + q);
-    if (lane < w.Bend - B16) sb[B16 - w.A4 + lane] = in[B16 + lane];
-  } else {
-    const uint64_t B4 = w.Bend & ~3ull;
-    const uint32_t nw = static_cast<uint32_t>((B4 - w.A4) / 4);
-    const uint32_t* inw = reinterpret_cast<const uint32_t*>(in + w.A4);
-    for (uint32_t q = lane; q < nw; q += 64) S[q] = __builtin_nontemporal_load(inw + q);
-    if (lane < w.Bend - B4) sb[B4 - w.A4 + lane] = in[B4 + lane];
-  }
-}
-
-// decode_kernel's byte-serial parse (parse_record_global), verbatim.
-__device__ __forceinline__ bool parse_global(const uint8_t* __restrict__ in, uint64_t o, uint64_t end, uint64_t& x,
-                                             uint32_t v[kLimbs]) {
-  bool ok = end > o;
-  const uint32_t xlen = ok ? in[o] : 0u;
-  x = 0;
-  ok = ok && xlen <= 8 && o + 1 + xlen <= end;
-  if (ok)
-    for (uint32_t i = 0; i < xlen; ++i) x = (x << 8) | in[o + 1 + i];
-#pragma unroll
-  for (int i = 0; i < kLimbs; ++i) v[i] = 0u;
-  if (ok) {
-    const uint64_t y0 = o + 1 + xlen;
-    uint64_t skip = 0;  // leading zero bytes are allowed (bytes_to_int ignores them)
-    while (y0 + skip < end && in[y0 + skip] == 0) ++skip;
-    const uint64_t sig = end - y0 - skip;
-    ok = sig <= 68;
-    if (ok) {
-      for (uint64_t i = 0; i < sig; ++i) {
-        const uint32_t byte = in[end - 1 - i];
-        v[i >> 2] |= byte << (8 * (i & 3));
-      }
-    }
-  }
-  return ok;
-}
-
-// decode_kernel's parse of one record from the staged window (its `if (valid)`
-// body on the LDS path), verbatim: v is zero unless the record is good.
-__device__ __forceinline__ bool parse_lds(const uint32_t* S, const Win& w, uint64_t oe, uint64_t ee, uint64_t& x,
-                                          uint32_t v[kLimbs]) {
-  const uint8_t* sb = reinterpret_cast<const uint8_t*>(S);
-#pragma unroll
-  for (int i = 0; i < kLimbs; ++i) v[i] = 0u;
-  x = 0;
-  // untrusted offsets: the record must lie inside this wave's window
-  bool ok = oe >= w.A && ee > oe && ee <= w.Bend;
-  const int32_t o = static_cast<int32_t>(oe - w.A4), end = static_cast<int32_t>(ee - w.A4);
-  const uint32_t xlen = ok ? sb[o] : 0u;
-  ok = ok && xlen <= 8 && o + 1 + static_cast<int32_t>(xlen) <= end;
-  if (ok) {
-    for (uint32_t i = 0; i < xlen; ++i) x = (x << 8) | sb[o + 1 + i];
-    int32_t ys = o + 1 + static_cast<int32_t>(xlen);
-    for (; end - ys > 68; ++ys)  // leading zero bytes beyond 68 (rare)
-      if (sb[ys]) {
-        ok = false;
-        break;
-      }
-    if (ok) {
-#pragma unroll
-      for (int i = 0; i < kLimbs; ++i) {
-        const int32_t q = end - 4 * (i + 1);  // window position of limb i's top byte
-        const int32_t nv = end - ys - 4 * i;  // bytes of limb i inside y
-        const int32_t qa = q < -4 ? -4 : q;   // stay inside the padded slice
-        const uint32_t lo = S[qa >> 2], hi = S[(qa >> 2) + 1];
-        uint32_t t = __builtin_bswap32(__builtin_amdgcn_alignbyte(hi, lo, static_cast<uint32_t>(qa) & 3u));
-        t = nv >= 4 ? t : (nv <= 0 ? 0u : (t & ((1u << (8 * nv)) - 1u)));
-        v[i] = t;
-      }
-    }
-  }
-  return ok;
-}
 
 // recon_finish (shamir_m521.hip) for element w of output tile `tile`: S
 // reduced, divided by d and 2^shift, stored; returns whether it is >= 2^64.
@@ -274,12 +88,6 @@ __device__ __forceinline__ bool finish(const Args& a, uint32_t tile, uint32_t w,
 #pragma unroll
   for (int l = 2; l < kLimbs; ++l) hi_or |= r[l];
   return hi_or != 0u;
-}
-
-__device__ __forceinline__ void lds_order() {
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 // Wire i of one lane: its record parsed from the staged window (or from
@@ -331,19 +139,10 @@ __device__ __forceinline__ void wave_end(const Args& a, uint32_t tile, uint32_t 
   }
 }
 
-// How a wave brings a window to LDS (measured in DESIGN.md §4.15):
-//   kSerial  the whole window into registers (every load issued before the
-//            first LDS store), then to LDS, then parsed: the product form
-//   kAhead   the same with wire i + 1's loads issued before wire i's
-//            arithmetic; no faster than kSerial at k = 3 and k = 5 (A/B only)
-//   kDirect  decode_kernel's staging loop as it stands (a load and its LDS
-//            store per step): fewer registers, 20-30 % slower here (A/B only)
-enum StageMode { kSerial = 0, kAhead = 1, kDirect = 2 };
-
 // A, INV as reconstruct_kernel's; K > 0: compile-time wire count (the wire
 // loop unrolled), K == 0: runtime count.
 template <int A, int INV, int K, int PF>
-__device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kRowWords]) {
+__device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kDecRowWords]) {
   constexpr int N = A + kLimbs;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -353,7 +152,7 @@ __device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kR
   const uint64_t e = e0 + lane;
   const bool valid = e < a.n_elem;
   const uint64_t eN = e0 + 64 < a.n_elem ? e0 + 64 : a.n_elem;
-  uint32_t* S = s_win[wv] + kDecPad / 4;  // S[j] = dword at window byte 4j
+  uint32_t* S = s_win[wv] + kWinPad / 4;  // S[j] = dword at window byte 4j
   const int32_t k = K > 0 ? K : a.k;
 
   uint32_t acc[N];
@@ -366,7 +165,7 @@ __device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kR
 #pragma unroll kUnroll
     for (int32_t i = 0; i < k; ++i) {
       const bool w16 = (a.w16 >> i) & 1u;
-      const Win cw = win_of(a.wire[i], w16, e0, eN);
+      const Win cw = win_of((OffTab)a.wire[i].offsets, a.wire[i].in_bytes, w16, e0, eN);
       uint64_t oe = 0, ee = 0;
       if (valid) {
         oe = a.wire[i].offsets[e];
@@ -379,7 +178,7 @@ __device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kR
     }
   } else {
     Stage st;
-    Win nw = win_of(a.wire[0], a.w16 & 1u, e0, eN);
+    Win nw = win_of((OffTab)a.wire[0].offsets, a.wire[0].in_bytes, a.w16 & 1u, e0, eN);
     uint64_t noe = 0, nee = 0;
     if (nw.lds) stage_load(st, a.wire[0].in, nw, a.w16 & 1u, lane);
     if (valid) {
@@ -394,7 +193,7 @@ __device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kR
       lds_order();
       if (PF == kAhead && i + 1 < k) {  // wire i + 1's loads go out before wire i's arithmetic
         const bool w16n = (a.w16 >> (i + 1)) & 1u;
-        nw = win_of(a.wire[i + 1], w16n, e0, eN);
+        nw = win_of((OffTab)a.wire[i + 1].offsets, a.wire[i + 1].in_bytes, w16n, e0, eN);
         if (nw.lds) stage_load(st, a.wire[i + 1].in, nw, w16n, lane);
         if (valid) {
           noe = a.wire[i + 1].offsets[e];
@@ -405,7 +204,7 @@ __device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kR
       lds_order();  // the slice is free for the next window
       if (PF == kSerial && i + 1 < k) {
         const bool w16n = (a.w16 >> (i + 1)) & 1u;
-        nw = win_of(a.wire[i + 1], w16n, e0, eN);
+        nw = win_of((OffTab)a.wire[i + 1].offsets, a.wire[i + 1].in_bytes, w16n, e0, eN);
         if (nw.lds) stage_load(st, a.wire[i + 1].in, nw, w16n, lane);
         if (valid) {
           noe = a.wire[i + 1].offsets[e];
@@ -419,7 +218,7 @@ __device__ __forceinline__ void records_body(const Args& a, uint32_t (*s_win)[kR
 
 template <int A, int INV, int K, int PF>
 __global__ void __launch_bounds__(kBlock) recon_records_kernel(const Args a) {
-  __shared__ __attribute__((aligned(16))) uint32_t s_win[kBlock / 64][kRowWords];
+  __shared__ __attribute__((aligned(16))) uint32_t s_win[kBlock / 64][kDecRowWords];
   records_body<A, INV, K, PF>(a, s_win);
 }
 

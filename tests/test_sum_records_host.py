@@ -2,9 +2,9 @@
 
 * the method, the binding and the C entry point exist, and the symbol is
   listed in _native.EXPORTS;
-* the window geometry csrc/sum_records.hip restates is decode_kernel's, so
-  wire_edges.decode_window predicts which waves take the byte-serial path
-  (test_gpu_sum_records.py relies on it);
+* (that wire_edges.decode_window predicts which waves take the byte-serial
+  path is test_wire_geom_host.py's: the window geometry is csrc/wire_geom.hpp's
+  for every kernel);
 * every argument error of the method fires before any device use (CPU
   tensors, no HIP device needed), and valid CPU arguments reach the device
   requirement and go no further;
@@ -25,12 +25,10 @@ import re
 import pytest
 import torch
 
-import wire_edges as we
 from delta_node.crypto import shamir
 from delta_node.crypto.shamir import _native, codec, field
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "delta-node_amd", "csrc")
 
 
 def test_method_binding_and_entry_point_exist():
@@ -39,27 +37,6 @@ def test_method_binding_and_entry_point_exist():
     assert hasattr(_native.lib(), "dn_m521_sum_records")
     assert "dn_m521_sum_records" in _native.EXPORTS
     assert "dn_m521_sum_records" in _native.exported_symbols()
-
-
-def _constant(text: str, name: str) -> str:
-    found = re.findall(r"^constexpr int " + name + r" = ([^;]+);", text, flags=re.M)
-    assert len(found) == 1, (name, found)
-    return found[0].strip()
-
-
-def test_window_geometry_is_decode_kernels():
-    """The constants that decide LDS path or byte-serial path read the same in
-    both translation units, and their value is wire_edges.DEC_WINDOW_LIMIT."""
-    with open(os.path.join(CSRC, "codec_m521.hip")) as f:
-        dec = f.read()
-    with open(os.path.join(CSRC, "sum_records.hip")) as f:
-        rec = f.read()
-    for name in ("kMaxRecord", "kDecPad", "kDecWindow"):
-        assert _constant(dec, name) == _constant(rec, name), name
-    assert _constant(rec, "kWinLimit") == "kDecWindow + 12"
-    assert "Bend - A4 <= static_cast<uint64_t>(kDecWindow) + 12u" in dec
-    assert _constant(rec, "kMaxRecord") == "1 + 8 + 66" and _constant(rec, "kDecWindow") == "64 * kMaxRecord + 8"
-    assert we.DEC_WINDOW_LIMIT == 64 * we.MAX_RECORD + 8 + 12 and we.MAX_RECORD == 1 + 8 + 66
 
 
 def group() -> int:

@@ -18,7 +18,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "delta-node_amd")
 SRCS = ["shamir_m521", "codec_m521", "aes_envelope", "mask_pcg64", "sum_i64", "mimc7_bn254", "mt19937_device",
-        "share_sum", "codec_many", "codec_frame"]
+        "share_sum", "recon_records", "codec_many", "sum_records", "codec_frame"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
