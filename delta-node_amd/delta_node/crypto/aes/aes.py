@@ -42,8 +42,21 @@ from typing import List, Optional, Union
 
 from ..shamir import _native
 
-EXPORTS = ("dn_aes_expand_key", "dn_aes_ctr", "dn_aes_encrypt_len", "dn_aes_encrypt", "dn_aes_decrypt_capacity",
-           "dn_aes_decrypt", "dn_aes_ctr_host", "dn_aes_encrypt_host", "dn_aes_decrypt_host", "dn_aes_host_impl", "dn_aes_expand_key_host")
+vp, u64, i32, cp = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p
+_SYMBOLS = {  # name -> (restype, argtypes, required), as _native._SYMBOLS
+    "dn_aes_expand_key": (i32, [cp, i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)], True),
+    "dn_aes_ctr": (i32, [cp, i32, cp, vp, vp, u64, vp], True),
+    "dn_aes_encrypt_len": (u64, [u64, i32], True),
+    "dn_aes_encrypt": (i32, [cp, i32, cp, vp, u64, vp, i32, vp], True),
+    "dn_aes_decrypt_capacity": (u64, [u64, i32], True),
+    "dn_aes_decrypt": (i32, [cp, i32, vp, u64, i32, vp, u64, vp, vp, vp], True),
+    "dn_aes_ctr_host": (i32, [cp, i32, cp, cp, vp, u64], True),
+    "dn_aes_encrypt_host": (i32, [cp, i32, cp, cp, u64, vp, i32], True),
+    "dn_aes_decrypt_host": (i32, [cp, i32, cp, u64, i32, vp, u64, ctypes.POINTER(ctypes.c_uint64)], True),
+    "dn_aes_host_impl": (i32, [], True),
+    "dn_aes_expand_key_host": (i32, [cp, i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)], True),
+}
+EXPORTS = tuple(_SYMBOLS)
 
 # byte-API messages up to this size are sealed / opened on the calling core
 # even on a GPU node (host AES-NI at ~2-4 GB/s beats H2D + launch + D2H below
@@ -52,33 +65,8 @@ HOST_MAX_BYTES = 1 << 20
 
 
 def _lib() -> ctypes.CDLL:
-    L = _native.lib()
-    if not getattr(L, "_dn_aes_bound", False):  # argtypes, once per loaded library
-        vp, u64, i32, cp = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p
-        L.dn_aes_expand_key.restype = i32
-        L.dn_aes_expand_key.argtypes = [cp, i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)]
-        L.dn_aes_ctr.restype = i32
-        L.dn_aes_ctr.argtypes = [cp, i32, cp, vp, vp, u64, vp]
-        L.dn_aes_encrypt_len.restype = u64
-        L.dn_aes_encrypt_len.argtypes = [u64, i32]
-        L.dn_aes_encrypt.restype = i32
-        L.dn_aes_encrypt.argtypes = [cp, i32, cp, vp, u64, vp, i32, vp]
-        L.dn_aes_decrypt_capacity.restype = u64
-        L.dn_aes_decrypt_capacity.argtypes = [u64, i32]
-        L.dn_aes_decrypt.restype = i32
-        L.dn_aes_decrypt.argtypes = [cp, i32, vp, u64, i32, vp, u64, vp, vp, vp]
-        L.dn_aes_ctr_host.restype = i32
-        L.dn_aes_ctr_host.argtypes = [cp, i32, cp, cp, vp, u64]
-        L.dn_aes_encrypt_host.restype = i32
-        L.dn_aes_encrypt_host.argtypes = [cp, i32, cp, cp, u64, vp, i32]
-        L.dn_aes_decrypt_host.restype = i32
-        L.dn_aes_decrypt_host.argtypes = [cp, i32, cp, u64, i32, vp, u64, ctypes.POINTER(ctypes.c_uint64)]
-        L.dn_aes_expand_key_host.restype = i32
-        L.dn_aes_expand_key_host.argtypes = [cp, i32, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32)]
-        L.dn_aes_host_impl.restype = i32
-        L.dn_aes_host_impl.argtypes = []
-        L._dn_aes_bound = True
-    return L
+    L = _native.lib()  # (the flag is looked at here: no further call once the library is bound)
+    return L if getattr(L, "_dn_aes_bound", False) else _native.bind(L, _SYMBOLS, "_dn_aes_bound")
 
 
 def _key(key) -> bytes:

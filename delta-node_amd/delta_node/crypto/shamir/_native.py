@@ -19,6 +19,8 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import _args
+
 DN_OK = 0
 DN_ERR_ARG = -1
 DN_ERR_THRESHOLD = -2
@@ -38,22 +40,6 @@ MAX_SHARES = 65535
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.normpath(os.path.join(_HERE, "..", "..", "..", "lib", "libdn_shamir.so"))
-
-# Every symbol include/dn_shamir.h declares (checked by the CPU test suite).
-EXPORTS = (
-    "dn_m521_vec_bytes", "dn_m521_split_u64", "dn_m521_split_fe", "dn_m521_lagrange",
-    "dn_m521_reconstruct", "dn_mt19937_draw_coeffs", "dn_last_error", "dn_version",
-    "dn_m521_split_prng", "dn_m521_prng_coeffs",
-    "dn_mt19937_device_scratch_bytes", "dn_mt19937_draw_coeffs_device", "dn_mt19937_skip",
-    "dn_mt19937_split_device", "dn_mt19937_split_supported", "dn_shamir_make_shares_host", "dn_shamir_resolve_shares_host",
-    "dn_shamir_eval_at_host", "dn_block_granularity", "dn_block_alloc", "dn_block_free", "dn_block_probe_rows",
-    "dn_block_record", "dn_block_ready", "dn_block_acquire", "dn_block_retired_bytes",
-    "dn_mt19937_rt_rows_embedded", "dn_mt19937_spec_stats", "dn_mt19937_jump_poly",
-    "dn_mt19937_split_many_scratch_bytes", "dn_mt19937_split_many_supported", "dn_mt19937_split_many_device",
-    "dn_m521_reconstruct_many_scratch_bytes", "dn_m521_reconstruct_many", "dn_m521_sum_vecs",
-    "dn_m521_reconstruct_records", "dn_m521_sum_records",
-)
-
 
 class Lagrange(ctypes.Structure):
     """Mirror of dn_m521_lagrange_t."""
@@ -79,6 +65,78 @@ class Segment(ctypes.Structure):
     """Mirror of dn_m521_segment_t."""
 
     _fields_ = [("n_elem", ctypes.c_uint64), ("shares", ctypes.c_void_p)]
+
+
+# Every symbol include/dn_shamir.h declares (checked by the CPU test suite):
+# name -> (restype, argtypes, required).  A library built from an older
+# revision (an A/B baseline) may lack the symbols that are not required: it
+# still loads, and calling one of them raises (`need`).
+vp, u64, i32, cp = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_char_p
+pvp, pu64, pu32, pi32 = (ctypes.POINTER(c) for c in (vp, u64, ctypes.c_uint32, ctypes.c_int32))
+_SYMBOLS = {
+    "dn_m521_vec_bytes": (u64, [u64], True),
+    "dn_m521_split_u64": (i32, [vp, vp, vp, u64, i32, i32, vp], True),
+    "dn_m521_split_fe": (i32, [vp, vp, vp, u64, i32, i32, vp], True),
+    "dn_m521_lagrange": (i32, [pu64, i32, i32, ctypes.POINTER(Lagrange)], True),
+    "dn_m521_reconstruct": (i32, [pvp, ctypes.POINTER(Lagrange), vp, vp, vp, u64, vp], True),
+    "dn_mt19937_draw_coeffs": (i32, [pu32, pi32, u64, i32, vp], True),
+    "dn_last_error": (cp, [], True),
+    "dn_version": (cp, [], True),
+    "dn_m521_split_prng": (i32, [vp, vp, u64, i32, u64, vp, u64, i32, i32, vp], True),
+    "dn_m521_prng_coeffs": (i32, [vp, u64, i32, u64, vp, u64, i32, vp], True),
+    "dn_mt19937_device_scratch_bytes": (u64, [u64, i32], True),
+    "dn_mt19937_draw_coeffs_device": (i32, [vp, vp, u64, i32, vp, vp, u64, vp], True),  # state, index by address
+    "dn_mt19937_skip": (i32, [pu32, pi32, u64], True),
+    "dn_mt19937_split_device": (i32, [vp, vp, vp, vp, u64, i32, i32, vp, u64, vp], True),
+    "dn_mt19937_split_supported": (i32, [u64, i32, i32], True),
+    "dn_shamir_make_shares_host": (i32, [cp, u64, cp, ctypes.c_uint32, i32, cp, ctypes.c_uint32, u64, vp, u64, vp],
+                                   True),
+    "dn_shamir_resolve_shares_host": (i32, [cp, vp, i32, i32, cp, ctypes.c_uint32, vp, u64, pu64], True),
+    "dn_shamir_eval_at_host": (i32, [cp, vp, cp, i32, cp, ctypes.c_uint32, i32, cp, ctypes.c_uint32, i32, vp, u64,
+                                     pu64, ctypes.POINTER(ctypes.c_int)], True),
+    "dn_block_granularity": (i32, [i32, pu64], True),
+    "dn_block_alloc": (i32, [u64, u64, i32, pvp], True),
+    "dn_block_free": (i32, [vp], True),
+    "dn_block_probe_rows": (i32, [vp, ctypes.c_uint32, u64, vp], True),
+    "dn_block_record": (i32, [vp, vp], True),
+    "dn_block_ready": (i32, [vp, vp, ctypes.POINTER(ctypes.c_int)], True),
+    "dn_block_acquire": (i32, [vp, vp, i32], True),
+    "dn_block_retired_bytes": (i32, [pu64], True),
+    "dn_mt19937_rt_rows_embedded": (i32, [], True),
+    "dn_mt19937_spec_stats": (i32, [pu64], False),
+    "dn_mt19937_jump_poly": (i32, [u64, pu64], False),
+    "dn_mt19937_split_many_scratch_bytes": (u64, [u64, i32, u64], False),
+    "dn_mt19937_split_many_supported": (i32, [u64, i32, i32, u64], False),
+    "dn_mt19937_split_many_device": (i32, [vp, vp, vp, ctypes.POINTER(Segment), u64, i32, i32, vp, u64, vp], False),
+    "dn_m521_reconstruct_many_scratch_bytes": (u64, [u64, i32], False),
+    "dn_m521_reconstruct_many": (i32, [pu64, pvp, pvp, pvp, vp, u64, ctypes.POINTER(Lagrange), vp, u64, vp], False),
+    "dn_m521_sum_vecs": (i32, [pvp, cp, u64, vp, u64, vp], False),
+    "dn_m521_reconstruct_records": (i32, [pvp, pu64, pvp, pu64, ctypes.POINTER(Lagrange), vp, vp, vp, vp, u64, vp],
+                                    False),
+    "dn_m521_sum_records": (i32, [pvp, pu64, pvp, u64, u64, cp, vp, vp, vp, u64, vp], False),
+}
+EXPORTS = tuple(_SYMBOLS)
+
+
+def bind(L: ctypes.CDLL, table: dict, flag: str) -> ctypes.CDLL:
+    """Give L's functions the restype / argtypes of a module's symbol table,
+    once per loaded library (`flag`, an attribute set on L: a library swapped
+    in by `library(path)` is bound again).  A required symbol that is missing
+    is an AttributeError here; another one is skipped."""
+    if not getattr(L, flag, False):
+        for name, (restype, argtypes, required) in table.items():
+            if required or hasattr(L, name):
+                fn = getattr(L, name)
+                fn.restype, fn.argtypes = restype, argtypes
+        setattr(L, flag, True)
+    return L
+
+
+def need(L: ctypes.CDLL, name: str) -> ctypes.CDLL:
+    """L, which must export `name` (a symbol its table does not require)."""
+    if not hasattr(L, name):
+        raise RuntimeError(f"{lib_path()} lacks {name}: rebuild the native library")
+    return L
 
 
 _lock = threading.Lock()
@@ -128,98 +186,7 @@ def _load(path: str) -> ctypes.CDLL:
             f"libdn_shamir.so not found at {path}: build it with `make -C delta-node_amd` "
             "(or __graft_entry__.build()); the Shamir hot path has no CPU fallback")
     L = ctypes.CDLL(path)
-    vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
-    L.dn_m521_vec_bytes.restype = u64
-    L.dn_m521_vec_bytes.argtypes = [u64]
-    L.dn_m521_split_u64.restype = i32
-    L.dn_m521_split_u64.argtypes = [vp, vp, vp, u64, i32, i32, vp]
-    L.dn_m521_split_fe.restype = i32
-    L.dn_m521_split_fe.argtypes = [vp, vp, vp, u64, i32, i32, vp]
-    L.dn_m521_lagrange.restype = i32
-    L.dn_m521_split_prng.restype = i32
-    L.dn_m521_split_prng.argtypes = [vp, vp, u64, i32, u64, vp, u64, i32, i32, vp]
-    L.dn_m521_prng_coeffs.restype = i32
-    L.dn_m521_prng_coeffs.argtypes = [vp, u64, i32, u64, vp, u64, i32, vp]
-    L.dn_m521_lagrange.argtypes = [ctypes.POINTER(ctypes.c_uint64), i32, i32, ctypes.POINTER(Lagrange)]
-    L.dn_m521_reconstruct.restype = i32
-    L.dn_m521_reconstruct.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(Lagrange), vp, vp, vp, u64, vp]
-    L.dn_mt19937_draw_coeffs.restype = i32
-    L.dn_mt19937_draw_coeffs.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32), u64,
-                                         i32, vp]
-    L.dn_mt19937_device_scratch_bytes.restype = u64
-    L.dn_mt19937_device_scratch_bytes.argtypes = [u64, i32]
-    L.dn_mt19937_draw_coeffs_device.restype = i32
-    L.dn_mt19937_draw_coeffs_device.argtypes = [vp, vp, u64, i32, vp, vp, u64, vp]  # state, index by address
-    L.dn_mt19937_split_device.restype = i32
-    L.dn_mt19937_split_device.argtypes = [vp, vp, vp, vp, u64, i32, i32, vp, u64, vp]
-    L.dn_mt19937_split_supported.restype = i32
-    L.dn_mt19937_split_supported.argtypes = [u64, i32, i32]
-    L.dn_shamir_make_shares_host.restype = i32
-    L.dn_shamir_make_shares_host.argtypes = [ctypes.c_char_p, u64, ctypes.c_char_p, ctypes.c_uint32, i32,
-                                             ctypes.c_char_p, ctypes.c_uint32, u64, vp, u64, vp]
-    L.dn_shamir_resolve_shares_host.restype = i32
-    L.dn_shamir_resolve_shares_host.argtypes = [ctypes.c_char_p, vp, i32, i32, ctypes.c_char_p, ctypes.c_uint32, vp,
-                                                u64, ctypes.POINTER(ctypes.c_uint64)]
-    L.dn_shamir_eval_at_host.restype = i32
-    L.dn_shamir_eval_at_host.argtypes = [ctypes.c_char_p, vp, ctypes.c_char_p, i32, ctypes.c_char_p,
-                                         ctypes.c_uint32, i32, ctypes.c_char_p, ctypes.c_uint32, i32, vp, u64,
-                                         ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_int)]
-    L.dn_block_granularity.restype = i32
-    L.dn_block_granularity.argtypes = [i32, ctypes.POINTER(ctypes.c_uint64)]
-    L.dn_block_alloc.restype = i32
-    L.dn_block_alloc.argtypes = [u64, u64, i32, ctypes.POINTER(ctypes.c_void_p)]
-    L.dn_block_free.restype = i32
-    L.dn_block_free.argtypes = [vp]
-    L.dn_block_record.restype = i32
-    L.dn_block_record.argtypes = [vp, vp]
-    L.dn_block_ready.restype = i32
-    L.dn_block_ready.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_int)]
-    L.dn_block_acquire.restype = i32
-    L.dn_block_acquire.argtypes = [vp, vp, i32]
-    L.dn_mt19937_rt_rows_embedded.restype = i32
-    L.dn_mt19937_rt_rows_embedded.argtypes = []
-    if hasattr(L, "dn_mt19937_spec_stats"):  # (an A/B baseline built from an older revision may lack these)
-        L.dn_mt19937_spec_stats.restype = i32
-        L.dn_mt19937_spec_stats.argtypes = [ctypes.POINTER(u64)]
-    if hasattr(L, "dn_mt19937_jump_poly"):
-        L.dn_mt19937_jump_poly.restype = i32
-        L.dn_mt19937_jump_poly.argtypes = [u64, ctypes.POINTER(u64)]
-    if hasattr(L, "dn_mt19937_split_many_device"):
-        L.dn_mt19937_split_many_scratch_bytes.restype = u64
-        L.dn_mt19937_split_many_scratch_bytes.argtypes = [u64, i32, u64]
-        L.dn_mt19937_split_many_supported.restype = i32
-        L.dn_mt19937_split_many_supported.argtypes = [u64, i32, i32, u64]
-        L.dn_mt19937_split_many_device.restype = i32
-        L.dn_mt19937_split_many_device.argtypes = [vp, vp, vp, ctypes.POINTER(Segment), u64, i32, i32, vp, u64, vp]
-    if hasattr(L, "dn_m521_reconstruct_many"):
-        L.dn_m521_reconstruct_many_scratch_bytes.restype = u64
-        L.dn_m521_reconstruct_many_scratch_bytes.argtypes = [u64, i32]
-        L.dn_m521_reconstruct_many.restype = i32
-        L.dn_m521_reconstruct_many.argtypes = [ctypes.POINTER(u64), ctypes.POINTER(vp), ctypes.POINTER(vp),
-                                               ctypes.POINTER(vp), vp, u64, ctypes.POINTER(Lagrange), vp, u64, vp]
-    if hasattr(L, "dn_m521_sum_vecs"):
-        L.dn_m521_sum_vecs.restype = i32
-        L.dn_m521_sum_vecs.argtypes = [ctypes.POINTER(vp), ctypes.c_char_p, u64, vp, u64, vp]
-    if hasattr(L, "dn_m521_reconstruct_records"):
-        L.dn_m521_reconstruct_records.restype = i32
-        L.dn_m521_reconstruct_records.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp),
-                                                  ctypes.POINTER(u64), ctypes.POINTER(Lagrange), vp, vp, vp, vp, u64,
-                                                  vp]
-    if hasattr(L, "dn_m521_sum_records"):
-        L.dn_m521_sum_records.restype = i32
-        L.dn_m521_sum_records.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(vp), u64, u64,
-                                          ctypes.c_char_p, vp, vp, vp, u64, vp]
-    L.dn_block_retired_bytes.restype = i32
-    L.dn_block_retired_bytes.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
-    L.dn_block_probe_rows.restype = i32
-    L.dn_block_probe_rows.argtypes = [vp, ctypes.c_uint32, u64, vp]
-    L.dn_mt19937_skip.restype = i32
-    L.dn_mt19937_skip.argtypes = [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32), u64]
-    L.dn_last_error.restype = ctypes.c_char_p
-    L.dn_last_error.argtypes = []
-    L.dn_version.restype = ctypes.c_char_p
-    L.dn_version.argtypes = []
-    return L
+    return bind(L, _SYMBOLS, "_dn_native_bound")
 
 
 def last_error() -> str:
@@ -365,9 +332,7 @@ def reconstruct_many(ns: Sequence[int], row_ptrs: Sequence[int], w: Lagrange, de
     m = len(ns)
     if len(row_ptrs) != m * w.k:
         raise ValueError("reconstruct_many: one row address per vector and weight")
-    L = lib()
-    if not hasattr(L, "dn_m521_reconstruct_many"):
-        raise RuntimeError(f"{lib_path()} lacks dn_m521_reconstruct_many: rebuild the native library")
+    L = need(lib(), "dn_m521_reconstruct_many")
     sb = int(L.dn_m521_reconstruct_many_scratch_bytes(m, w.k))
     scratch = torch.empty(sb, dtype=torch.uint8, device=device)
     arr = ctypes.c_void_p * m
@@ -377,18 +342,32 @@ def reconstruct_many(ns: Sequence[int], row_ptrs: Sequence[int], w: Lagrange, de
                                      ctypes.byref(w), scratch.data_ptr(), sb, stream_ptr()))
 
 
+def _negate_bytes(negate: Optional[Sequence[bool]], m: int, complaint: str) -> Optional[bytes]:
+    """The m negate flags as the bytes the sum entry points read (None: none)."""
+    if negate is None:
+        return None
+    neg = bytes(1 if f else 0 for f in negate)
+    if len(neg) != m:
+        raise ValueError(complaint)
+    return neg
+
+
+def _wire_arrays(wires: Sequence):
+    """Wire triples (records address, byte count, offsets address) as the
+    three parallel arrays the record entry points read."""
+    m = max(len(wires), 1)
+    return ((ctypes.c_void_p * m)(*[p for p, _, _ in wires]), (ctypes.c_uint64 * m)(*[b for _, b, _ in wires]),
+            (ctypes.c_void_p * m)(*[o for _, _, o in wires]))
+
+
 def sum_vecs(ptrs: Sequence[int], negate: Optional[Sequence[bool]], out_ptr: int, n_tiles: int) -> None:
     """out = sum_i +-vecs_i mod p over n_tiles tiles (dn_m521_sum_vecs): ptrs
     the m device addresses, negate m flags (true: subtract) or None, out_ptr
     the output's address (it may be one of ptrs).  Any m: the entry point
     chains launches of DN_M521_SUM_GROUP inputs.  Does not synchronise."""
-    L = lib()
-    if not hasattr(L, "dn_m521_sum_vecs"):
-        raise RuntimeError(f"{lib_path()} lacks dn_m521_sum_vecs: rebuild the native library")
+    L = need(lib(), "dn_m521_sum_vecs")
     m = len(ptrs)
-    neg = None if negate is None else bytes(1 if f else 0 for f in negate)
-    if neg is not None and len(neg) != m:
-        raise ValueError("sum_vecs: one negate flag per input")
+    neg = _negate_bytes(negate, m, "sum_vecs: one negate flag per input")
     check(L.dn_m521_sum_vecs((ctypes.c_void_p * max(m, 1))(*ptrs), neg, m, out_ptr, n_tiles, stream_ptr()))
 
 
@@ -400,18 +379,13 @@ def reconstruct_records(wires: Sequence, xs: Sequence[int], w: Lagrange, bad, ou
     `lagrange(xs, t)`, bad a device int32 / uint32 tensor [2] the kernel ADDS
     its two counts to (unrepresentable records, records whose x is not xs[i]).
     Outputs as `reconstruct`.  Does not synchronise."""
-    L = lib()
-    if not hasattr(L, "dn_m521_reconstruct_records"):
-        raise RuntimeError(f"{lib_path()} lacks dn_m521_reconstruct_records: rebuild the native library")
+    L = need(lib(), "dn_m521_reconstruct_records")
     k = len(wires)
     if k != w.k or k != len(xs):
         raise ValueError("reconstruct_records: one wire and one abscissa per weight")
-    m = max(k, 1)
-    check(L.dn_m521_reconstruct_records((ctypes.c_void_p * m)(*[p for p, _, _ in wires]),
-                                        (ctypes.c_uint64 * m)(*[b for _, b, _ in wires]),
-                                        (ctypes.c_void_p * m)(*[o for _, _, o in wires]),
-                                        (ctypes.c_uint64 * m)(*[int(x) for x in xs]), ctypes.byref(w), _ptr(out_fe),
-                                        _ptr(out_u64), _ptr(overflow), _ptr(bad), n, stream_ptr()))
+    check(L.dn_m521_reconstruct_records(*_wire_arrays(wires), (ctypes.c_uint64 * max(k, 1))(*[int(x) for x in xs]),
+                                        ctypes.byref(w), _ptr(out_fe), _ptr(out_u64), _ptr(overflow), _ptr(bad), n,
+                                        stream_ptr()))
 
 
 def sum_records(wires: Sequence, x: int, negate: Optional[Sequence[bool]], bad, out, acc=None, n: int = 0) -> None:
@@ -424,20 +398,13 @@ def sum_records(wires: Sequence, x: int, negate: Optional[Sequence[bool]], bad, 
     uint8 device vectors of n elements (acc may be out, or None).  Any m >= 1:
     the entry point chains launches of DN_M521_SUM_RECORDS_GROUP wires.  Does
     not synchronise."""
-    L = lib()
-    if not hasattr(L, "dn_m521_sum_records"):
-        raise RuntimeError(f"{lib_path()} lacks dn_m521_sum_records: rebuild the native library")
+    L = need(lib(), "dn_m521_sum_records")
     m = len(wires)
-    neg = None if negate is None else bytes(1 if f else 0 for f in negate)
-    if neg is not None and len(neg) != m:
-        raise ValueError("sum_records: one negate flag per wire")
-    if not 0 <= int(x) < (1 << 64):
+    neg = _negate_bytes(negate, m, "sum_records: one negate flag per wire")
+    if not _args.fits_u64(int(x)):
         raise ValueError("sum_records: x must fit 64 bits")
-    k = max(m, 1)
-    check(L.dn_m521_sum_records((ctypes.c_void_p * k)(*[p for p, _, _ in wires]),
-                                (ctypes.c_uint64 * k)(*[b for _, b, _ in wires]),
-                                (ctypes.c_void_p * k)(*[o for _, _, o in wires]), m, int(x), neg, _ptr(acc),
-                                _ptr(out), _ptr(bad), n, stream_ptr()))
+    check(L.dn_m521_sum_records(*_wire_arrays(wires), m, int(x), neg, _ptr(acc), _ptr(out), _ptr(bad), n,
+                                stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:
@@ -533,11 +500,8 @@ def mt_compatible(rng) -> bool:
 
 def _mt_inplace(rng):
     """(uint32* state, int32* index) into rng's own MT19937 state, or None."""
-    lay = _mt_layout()
-    if not lay or not mt_compatible(rng):
-        return None
-    return (ctypes.cast(id(rng) + lay[1], ctypes.POINTER(ctypes.c_uint32)),
-            ctypes.cast(id(rng) + lay[0], ctypes.POINTER(ctypes.c_int32)))
+    ip = _mt_inplace_addr(rng)
+    return ip and (ctypes.cast(ip[0], pu32), ctypes.cast(ip[1], pi32))
 
 
 def _mt_inplace_addr(rng):
@@ -573,6 +537,43 @@ def _mt_scratch(nbytes: int, device):
     return buf
 
 
+def _mt_device_draw(rng, launch) -> bool:
+    """The state hand-over of a device draw: `launch(state address, index
+    address)` is the entry point's return code, on rng's own MT19937 state
+    (taken in place) or on a marshalled copy that is written back on success
+    only — the entry points write the state only on success, so rng is
+    untouched on False (a rejected draw, a stream beyond the jump table: redo
+    it on the host) and on an exception."""
+    ip = _mt_inplace_addr(rng)
+    if ip:
+        rc = launch(*ip)
+    else:
+        version, gauss, state, index = _mt_state(rng)
+        rc = launch(ctypes.addressof(state), ctypes.addressof(index))
+    if rc in (DN_ERR_RETRY, DN_ERR_UNSUPPORTED):
+        return False
+    check(rc)
+    if not ip:
+        _mt_set_state(rng, version, gauss, state, index)
+    return True
+
+
+_MT_SHAPES: dict = {}  # (library, n, t, n_shares[, segments]) -> (fused form supported, scratch bytes)
+
+
+def _mt_shape(key: tuple, supported, scratch_bytes) -> tuple:
+    """The cached (supported, scratch bytes) of a fused draw's shape: two C
+    calls per new shape only."""
+    shape = _MT_SHAPES.get(key)
+    if shape is None:
+        sup = bool(supported())
+        shape = (sup, int(scratch_bytes()) if sup else 0)
+        if len(_MT_SHAPES) >= 256:
+            _MT_SHAPES.clear()
+        _MT_SHAPES[key] = shape
+    return shape
+
+
 def mt_draw_coeffs_device(rng, n: int, tm1: int, out) -> bool:
     """`mt_draw_coeffs` with the coefficients generated on the GPU into `out`
     (uint8 device tensor [tm1, vec_bytes(n)]), bit-exact; `rng` advances
@@ -589,23 +590,10 @@ def mt_draw_coeffs_device(rng, n: int, tm1: int, out) -> bool:
     L = lib()
     sb = int(L.dn_mt19937_device_scratch_bytes(n, tm1))
     scratch = _mt_scratch(sb, out.device)
-    ip = _mt_inplace_addr(rng)  # the entry point writes the state only on success
-    if ip:
-        rc = L.dn_mt19937_draw_coeffs_device(ip[0], ip[1], n, tm1, out.data_ptr(), scratch.data_ptr(), sb,
-                                             stream_ptr())
-    else:
-        version, gauss, state, index = _mt_state(rng)
-        rc = L.dn_mt19937_draw_coeffs_device(ctypes.addressof(state), ctypes.addressof(index), n, tm1,
-                                             out.data_ptr(), scratch.data_ptr(), sb, stream_ptr())
-    if rc in (DN_ERR_RETRY, DN_ERR_UNSUPPORTED):
-        return False
-    check(rc)
-    if not ip:
-        _mt_set_state(rng, version, gauss, state, index)
-    return True
+    return _mt_device_draw(rng, lambda state, index: L.dn_mt19937_draw_coeffs_device(
+        state, index, n, tm1, out.data_ptr(), scratch.data_ptr(), sb, stream_ptr()))
 
 
-_MT_SPLIT_SHAPES: dict = {}  # (library, n, t, n_shares) -> (fused split supported, scratch bytes)
 
 
 def mt_split_device(rng, secrets, shares, n: int, t: int, n_shares: int) -> bool:
@@ -619,14 +607,8 @@ def mt_split_device(rng, secrets, shares, n: int, t: int, n_shares: int) -> bool
     if n == 0:
         return True
     L = lib()
-    key = (id(L), n, t, n_shares)
-    shape = _MT_SPLIT_SHAPES.get(key)  # (supported, scratch bytes): two C calls per new shape only
-    if shape is None:
-        sup = bool(L.dn_mt19937_split_supported(n, t, n_shares))
-        shape = (sup, int(L.dn_mt19937_device_scratch_bytes(n, t - 1)) if sup else 0)
-        if len(_MT_SPLIT_SHAPES) >= 256:
-            _MT_SPLIT_SHAPES.clear()
-        _MT_SPLIT_SHAPES[key] = shape
+    shape = _mt_shape((id(L), n, t, n_shares), lambda: L.dn_mt19937_split_supported(n, t, n_shares),
+                      lambda: L.dn_mt19937_device_scratch_bytes(n, t - 1))
     if not shape[0]:
         return False  # before any allocation: the draw, then the split
     for name, x in (("secrets", secrets), ("shares", shares)):
@@ -634,23 +616,8 @@ def mt_split_device(rng, secrets, shares, n: int, t: int, n_shares: int) -> bool
             raise ValueError(f"mt_split_device: {name} must be a contiguous tensor on the shares' HIP device")
     sb = shape[1]
     scratch = _mt_scratch(sb, shares.device)
-    ip = _mt_inplace_addr(rng)  # the entry point writes the state only on success
-    if ip:
-        rc = L.dn_mt19937_split_device(ip[0], ip[1], secrets.data_ptr(), shares.data_ptr(), n, t, n_shares,
-                                       scratch.data_ptr(), sb, stream_ptr())
-    else:
-        version, gauss, state, index = _mt_state(rng)
-        rc = L.dn_mt19937_split_device(ctypes.addressof(state), ctypes.addressof(index), secrets.data_ptr(),
-                                       shares.data_ptr(), n, t, n_shares, scratch.data_ptr(), sb, stream_ptr())
-    if rc in (DN_ERR_RETRY, DN_ERR_UNSUPPORTED):
-        return False
-    check(rc)
-    if not ip:
-        _mt_set_state(rng, version, gauss, state, index)
-    return True
-
-
-_MT_MANY_SHAPES: dict = {}  # (library, n_total, t, n_shares, segments) -> (supported, scratch bytes)
+    return _mt_device_draw(rng, lambda state, index: L.dn_mt19937_split_device(
+        state, index, secrets.data_ptr(), shares.data_ptr(), n, t, n_shares, scratch.data_ptr(), sb, stream_ptr()))
 
 
 def mt_split_many_device(rng, secrets, segs, t: int, n_shares: int) -> bool:
@@ -666,17 +633,10 @@ def mt_split_many_device(rng, secrets, segs, t: int, n_shares: int) -> bool:
     n_total = sum(n for n, _ in segs)
     if n_total == 0:
         return True
-    L = lib()
-    if not hasattr(L, "dn_mt19937_split_many_device"):
-        raise RuntimeError(f"{lib_path()} lacks dn_mt19937_split_many_device: rebuild the native library")
-    key = (id(L), n_total, t, n_shares, len(segs))
-    shape = _MT_MANY_SHAPES.get(key)
-    if shape is None:
-        sup = bool(L.dn_mt19937_split_many_supported(n_total, t, n_shares, len(segs)))
-        shape = (sup, int(L.dn_mt19937_split_many_scratch_bytes(n_total, t - 1, len(segs))) if sup else 0)
-        if len(_MT_MANY_SHAPES) >= 256:
-            _MT_MANY_SHAPES.clear()
-        _MT_MANY_SHAPES[key] = shape
+    L = need(lib(), "dn_mt19937_split_many_device")
+    shape = _mt_shape((id(L), n_total, t, n_shares, len(segs)),
+                      lambda: L.dn_mt19937_split_many_supported(n_total, t, n_shares, len(segs)),
+                      lambda: L.dn_mt19937_split_many_scratch_bytes(n_total, t - 1, len(segs)))
     if not shape[0]:
         return False  # before any allocation: the per-tensor calls
     dev = secrets.device
@@ -685,20 +645,8 @@ def mt_split_many_device(rng, secrets, segs, t: int, n_shares: int) -> bool:
     table = (Segment * len(segs))(*segs)
     sb = shape[1]
     scratch = _mt_scratch(sb, dev)
-    ip = _mt_inplace_addr(rng)  # the entry point writes the state only on success
-    if ip:
-        rc = L.dn_mt19937_split_many_device(ip[0], ip[1], secrets.data_ptr(), table, len(segs), t, n_shares,
-                                            scratch.data_ptr(), sb, stream_ptr())
-    else:
-        version, gauss, state, index = _mt_state(rng)
-        rc = L.dn_mt19937_split_many_device(ctypes.addressof(state), ctypes.addressof(index), secrets.data_ptr(),
-                                            table, len(segs), t, n_shares, scratch.data_ptr(), sb, stream_ptr())
-    if rc in (DN_ERR_RETRY, DN_ERR_UNSUPPORTED):
-        return False
-    check(rc)
-    if not ip:
-        _mt_set_state(rng, version, gauss, state, index)
-    return True
+    return _mt_device_draw(rng, lambda state, index: L.dn_mt19937_split_many_device(
+        state, index, secrets.data_ptr(), table, len(segs), t, n_shares, scratch.data_ptr(), sb, stream_ptr()))
 
 
 def mt_jump_poly(words: int):

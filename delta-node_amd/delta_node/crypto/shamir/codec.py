@@ -22,48 +22,30 @@ from __future__ import annotations
 import ctypes
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
-from . import _native, field
+from . import _args, _native, field
 
-EXPORTS = ("dn_m521_codec_scratch_bytes", "dn_m521_encoded_capacity", "dn_m521_encode_shares",
-           "dn_m521_decode_shares", "dn_m521_encode_many_scratch_bytes", "dn_m521_encode_shares_many",
-           "dn_m521_frame_records_offset", "dn_m521_frame_capacity", "dn_m521_frame_finish",
-           "dn_m521_frame_scratch_bytes", "dn_m521_frame_open")
+vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
+pvp, pu64 = ctypes.POINTER(vp), ctypes.POINTER(u64)
+_SYMBOLS = {  # name -> (restype, argtypes, required), as _native._SYMBOLS
+    "dn_m521_codec_scratch_bytes": (u64, [u64], True),
+    "dn_m521_encoded_capacity": (u64, [u64, u64], True),
+    "dn_m521_encode_shares": (i32, [vp, u64, u64, vp, vp, u64, vp, u64, vp], True),
+    "dn_m521_decode_shares": (i32, [vp, u64, vp, u64, vp, vp, vp, vp], True),
+    "dn_m521_encode_many_scratch_bytes": (u64, [u64, u64, u64], False),
+    "dn_m521_encode_shares_many": (i32, [pu64, pvp, pu64, u64, ctypes.POINTER(ctypes.c_uint32), pu64, pvp, pvp, pu64,
+                                         u64, vp, vp, u64, vp], False),
+    "dn_m521_frame_records_offset": (u64, [u64], False),
+    "dn_m521_frame_capacity": (u64, [u64, u64], False),
+    "dn_m521_frame_finish": (i32, [pvp, pvp, pu64, u64, u64, vp], False),
+    "dn_m521_frame_scratch_bytes": (u64, [u64, u64], False),
+    "dn_m521_frame_open": (i32, [pvp, pu64, pu64, u64, u64, pvp, vp, vp, u64, vp], False),
+}
+EXPORTS = tuple(_SYMBOLS)
 
 
 def _lib():
-    L = _native.lib()
-    if not getattr(L, "_dn_codec_bound", False):  # argtypes, once per loaded library
-        vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
-        L.dn_m521_codec_scratch_bytes.restype = u64
-        L.dn_m521_codec_scratch_bytes.argtypes = [u64]
-        L.dn_m521_encoded_capacity.restype = u64
-        L.dn_m521_encoded_capacity.argtypes = [u64, u64]
-        L.dn_m521_encode_shares.restype = i32
-        L.dn_m521_encode_shares.argtypes = [vp, u64, u64, vp, vp, u64, vp, u64, vp]
-        L.dn_m521_decode_shares.restype = i32
-        L.dn_m521_decode_shares.argtypes = [vp, u64, vp, u64, vp, vp, vp, vp]
-        if hasattr(L, "dn_m521_encode_shares_many"):  # (an A/B baseline built from an older revision lacks these)
-            L.dn_m521_encode_many_scratch_bytes.restype = u64
-            L.dn_m521_encode_many_scratch_bytes.argtypes = [u64, u64, u64]
-            L.dn_m521_encode_shares_many.restype = i32
-            L.dn_m521_encode_shares_many.argtypes = [ctypes.POINTER(u64), ctypes.POINTER(vp), ctypes.POINTER(u64), u64,
-                                                     ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(u64),
-                                                     ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(u64), u64,
-                                                     vp, vp, u64, vp]
-        if hasattr(L, "dn_m521_frame_open"):
-            L.dn_m521_frame_records_offset.restype = u64
-            L.dn_m521_frame_records_offset.argtypes = [u64]
-            L.dn_m521_frame_capacity.restype = u64
-            L.dn_m521_frame_capacity.argtypes = [u64, u64]
-            L.dn_m521_frame_finish.restype = i32
-            L.dn_m521_frame_finish.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(u64), u64, u64, vp]
-            L.dn_m521_frame_scratch_bytes.restype = u64
-            L.dn_m521_frame_scratch_bytes.argtypes = [u64, u64]
-            L.dn_m521_frame_open.restype = i32
-            L.dn_m521_frame_open.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(u64), ctypes.POINTER(u64), u64, u64,
-                                             ctypes.POINTER(vp), vp, vp, u64, vp]
-        L._dn_codec_bound = True
-    return L
+    L = _native.lib()  # (the flag is looked at here: no further call once the library is bound)
+    return L if getattr(L, "_dn_codec_bound", False) else _native.bind(L, _SYMBOLS, "_dn_codec_bound")
 
 
 _scratch_cache = {}  # (device index, stream) -> uint8 scratch tensor (grown on demand)
@@ -93,20 +75,28 @@ def _out(t, numel: int, dtype, dev, what: str):
     return t
 
 
+def _wire_out(t, cap: int, dev, what: str):
+    """A wire buffer: the caller's (>= cap bytes, 4-byte aligned) or a fresh one."""
+    import torch
+
+    t = _out(t, max(cap, 1), torch.uint8, dev, what)
+    if t.data_ptr() & 3:
+        raise ValueError(f"{what}: the buffer must be 4-byte aligned (the encoder stores dwords)")
+    return t
+
+
 def encode_share_vec(vec, n: int, x: int, *, trim: bool = True, out=None, offsets=None):
     """Share x of n elements (uint8 device tensor, tiled) -> (packed uint8, offsets int64[n+1]).
     out / offsets: caller buffers (>= encoded_capacity(n, x) bytes, 4-byte aligned; >= n + 1 entries), else allocated.
     trim=True cuts `packed` to its length (one read-back of offsets[n])."""
     import torch
 
-    if not 0 <= x < (1 << 64):
+    if not _args.fits_u64(x):
         raise NotImplementedError("encode_share_vec: x must fit 64 bits")
     L = _lib()
     dev = vec.device
     cap = int(L.dn_m521_encoded_capacity(n, x))
-    out = _out(out, max(cap, 1), torch.uint8, dev, "encode_share_vec out")
-    if out.data_ptr() & 3:
-        raise ValueError("encode_share_vec out: the buffer must be 4-byte aligned (the encoder stores dwords)")
+    out = _wire_out(out, cap, dev, "encode_share_vec out")
     # every entry is written by the encoder (offsets[n] by the last element)
     if n:
         offsets = _out(offsets, n + 1, torch.int64, dev, "encode_share_vec offsets")[: n + 1]
@@ -165,36 +155,45 @@ def encode_shares_many(blocks, ns: Sequence[int], xs: Optional[Sequence[int]] = 
     `SecretShare.resolve_records_vec`, whose result the caller splits by `ns`.
     Argument errors are raised before any device use; n_total == 0 gives empty
     wires with offsets == [0]."""
+    return _encode_list("encode_shares_many", lambda: _native.need(_lib(), "dn_m521_encode_shares_many"), False,
+                        blocks, ns, xs, rows, trim, outs, offsets)
+
+
+def _encode_list(what: str, library, framed: bool, blocks, ns, xs, rows, trim: bool, outs, offsets):
+    """encode_shares_many (framed=False: wire i's records at the start of its
+    buffer, a `_wire_out`) and encode_frames_many (framed=True: at R(n_total)
+    of a `_frame_out`, then one finish launch for all wires)."""
     import torch
 
-    what = "encode_shares_many"
     ns, ptrs, pitches, tiles, xs, rows, dev = _many_args(what, blocks, ns, xs, rows, outs, offsets)
     if not xs:
         return []
     n_total = sum(ns)
     dev = _many_device(what, dev)
-    L = _lib()
-    if not hasattr(L, "dn_m521_encode_shares_many"):
-        raise RuntimeError(f"{_native.lib_path()} lacks dn_m521_encode_shares_many: rebuild the native library")
+    L = library()
     m = len(xs)
+    R = int(L.dn_m521_frame_records_offset(n_total)) if framed else 0
     caps = [int(L.dn_m521_encoded_capacity(n_total, x)) for x in xs]
-    packed, offs = [], []
+    buffer = _frame_out if framed else _wire_out
+    bufs, offs = [], []
     for i in range(m):
-        o = _out(None if outs is None else outs[i], max(caps[i], 1), torch.uint8, dev, f"{what} outs[{i}]")
-        if o.data_ptr() & 3:
-            raise ValueError(f"{what} outs[{i}]: the buffer must be 4-byte aligned (the encoder stores dwords)")
-        packed.append(o)
+        bufs.append(buffer(None if outs is None else outs[i], R + caps[i], dev, f"{what} outs[{i}]"))
         # every entry is written by the encoder (offsets[n_total] by the list's last element)
         offs.append(_out(None if offsets is None else offsets[i], n_total + 1, torch.int64, dev,
                          f"{what} offsets[{i}]")[: n_total + 1])
-    if n_total == 0:
+    totals = None
+    if n_total:
+        totals = _encode_many(L, ns, ptrs, pitches, tiles, xs, rows, [b[R:] for b in bufs] if framed else bufs, offs,
+                              caps, dev)
+    else:
         for o in offs:
             o.zero_()
-        return [(p[:0] if trim else p, o) for p, o in zip(packed, offs)]
-    totals = _encode_many(L, ns, ptrs, pitches, tiles, xs, rows, packed, offs, caps, dev)
+    if framed:
+        _finish(L, offs, bufs, xs, n_total)
     if trim:
-        packed = [p[:t] for p, t in zip(packed, totals.tolist())]  # one read-back for all wires
-    return list(zip(packed, offs))
+        lens = totals.tolist() if totals is not None else [0] * m  # one read-back for all wires
+        bufs = [b[: R + t] for b, t in zip(bufs, lens)]
+    return list(zip(bufs, offs))
 
 
 def _many_args(what: str, blocks, ns, xs, rows, outs, offsets):
@@ -231,7 +230,7 @@ def _many_args(what: str, blocks, ns, xs, rows, outs, offsets):
             raise ValueError(f"{what}: rows without xs")
         xs = range(1, (S or 0) + 1)
     xs = [int(x) for x in xs]
-    if any(not 0 <= x < (1 << 64) for x in xs):
+    if not all(_args.fits_u64(x) for x in xs):
         raise NotImplementedError(f"{what}: x must fit 64 bits")
     rows = [x - 1 for x in xs] if rows is None else [int(r) for r in rows]
     if len(rows) != len(xs):
@@ -350,10 +349,7 @@ FRAME_HEADER = 32
 
 
 def _frame_lib():
-    L = _lib()
-    if not hasattr(L, "dn_m521_frame_open"):
-        raise RuntimeError(f"{_native.lib_path()} lacks dn_m521_frame_open: rebuild the native library")
-    return L
+    return _native.need(_lib(), "dn_m521_frame_open")
 
 
 def frame_records_offset(n: int) -> int:
@@ -402,7 +398,7 @@ def encode_share_frame(vec, n: int, x: int, *, trim: bool = True, out=None, offs
     n, x = int(n), int(x)
     if n < 0:
         raise ValueError(f"{what}: n must not be negative")
-    if not 0 <= x < (1 << 64):
+    if not _args.fits_u64(x):
         raise NotImplementedError(f"{what}: x must fit 64 bits")
     vb = field.vec_bytes(n)
     if not (isinstance(vec, torch.Tensor) and vec.dtype == torch.uint8 and vec.is_contiguous() and vec.numel() >= vb):
@@ -450,34 +446,7 @@ def encode_frames_many(blocks, ns: Sequence[int], xs: Optional[Sequence[int]] = 
     Returns one (frame, offsets[: n_total + 1]) per x; frame[R(n_total):] with
     the offsets is the wire encode_shares_many returns.  n_total == 0 gives
     header-only frames."""
-    import torch
-
-    what = "encode_frames_many"
-    ns, ptrs, pitches, tiles, xs, rows, dev = _many_args(what, blocks, ns, xs, rows, outs, offsets)
-    if not xs:
-        return []
-    n_total = sum(ns)
-    dev = _many_device(what, dev)
-    L = _frame_lib()
-    m = len(xs)
-    R = int(L.dn_m521_frame_records_offset(n_total))
-    caps = [int(L.dn_m521_encoded_capacity(n_total, x)) for x in xs]
-    frames, offs = [], []
-    for i in range(m):
-        frames.append(_frame_out(None if outs is None else outs[i], R + caps[i], dev, f"{what} outs[{i}]"))
-        offs.append(_out(None if offsets is None else offsets[i], n_total + 1, torch.int64, dev,
-                         f"{what} offsets[{i}]")[: n_total + 1])
-    totals = None
-    if n_total:
-        totals = _encode_many(L, ns, ptrs, pitches, tiles, xs, rows, [f[R:] for f in frames], offs, caps, dev)
-    else:
-        for o in offs:
-            o.zero_()
-    _finish(L, offs, frames, xs, n_total)
-    if trim:
-        lens = totals.tolist() if totals is not None else [0] * m  # one read-back for all wires
-        frames = [f[: R + t] for f, t in zip(frames, lens)]
-    return list(zip(frames, offs))
+    return _encode_list("encode_frames_many", _frame_lib, True, blocks, ns, xs, rows, trim, outs, offsets)
 
 
 def _headers(frames, what: str):
@@ -537,7 +506,7 @@ def open_frames(frames, n: Optional[int], xs: Optional[Sequence[int]], *, offset
         xs = [int(x) for x in xs]
         if len(xs) != m:
             raise ValueError(f"{what}: {len(xs)} abscissas for {m} frames")
-        if any(not 0 <= x < (1 << 64) for x in xs):
+        if not all(_args.fits_u64(x) for x in xs):
             raise ValueError(f"{what}: x must fit 64 bits")
     if offsets is not None:
         offsets = list(offsets)
@@ -547,9 +516,7 @@ def open_frames(frames, n: Optional[int], xs: Optional[Sequence[int]], *, offset
             if not (isinstance(o, torch.Tensor) and o.dtype == torch.int64 and o.dim() == 1 and o.is_contiguous()
                     and o.device == first.device):
                 raise ValueError(f"{what}: offsets must be contiguous 1-D int64 tensors on the frames' device")
-    if bad is not None and not (isinstance(bad, torch.Tensor) and bad.dtype == torch.int32
-                                and tuple(bad.shape) == (2,) and bad.is_contiguous() and bad.device == first.device):
-        raise ValueError(f"{what}: bad must be a contiguous int32 tensor [2] on the frames' device")
+    _args.check_bad_flag(what, bad, first.device, "frames")
     L = _frame_lib()
 
     def sizes(n: int) -> int:
@@ -580,9 +547,7 @@ def open_frames(frames, n: Optional[int], xs: Optional[Sequence[int]], *, offset
     frames = [f.clone() if f.data_ptr() & 15 else f for f in frames]
     offs = [_out(None if offsets is None else offsets[i], n + 1, torch.int64, dev, f"{what} offsets[{i}]")[: n + 1]
             for i in range(m)]
-    checked = bad is None
-    if checked:
-        bad = torch.zeros(2, dtype=torch.int32, device=dev)
+    bad, checked = _args.bad_flag(bad, dev)
     sb = int(L.dn_m521_frame_scratch_bytes(n, m))
     scratch = _scratch(dev, sb)
     vps, u64s = ctypes.c_void_p * m, ctypes.c_uint64 * m

@@ -38,7 +38,7 @@ from functools import reduce
 from typing import List, Optional, Sequence, Tuple, Union
 
 from ... import serialize
-from . import _native, field, memory, op
+from . import _args, _native, field, memory, op
 
 __all__ = ["Share", "PRIME", "SecretShare"]
 
@@ -173,7 +173,7 @@ def _resolve_vectors(vecs: Sequence, xs: Sequence[int], n: int, threshold: int,
     import torch
 
     k = len(xs)
-    if k <= _native.MAX_RESOLVE and all(0 <= int(x) < (1 << 64) for x in xs):
+    if k <= _native.MAX_RESOLVE and all(_args.fits_u64(int(x)) for x in xs):
         w = _native.lagrange(xs, threshold)
         _native.reconstruct(vecs, w, out_fe=out_fe, out_u64=out_u64, overflow=overflow, n=n)
         return
@@ -342,10 +342,7 @@ class SecretShare(object):
         self._require_m521()
         import torch
 
-        if self.threshold > shares:
-            raise ValueError("threshold should be little equal than shares")
-        if shares > _native.MAX_SHARES or self.threshold > _native.MAX_THRESHOLD:
-            raise NotImplementedError("make_shares_vec: at most 65535 shares and threshold 64")
+        _args.check_limits("make_shares_vec", self.threshold, shares, _native.MAX_SHARES, _native.MAX_THRESHOLD)
         dev = _device()
         vals = _device_values(values, dev, "make_shares_vec")
         n = vals.numel()
@@ -353,9 +350,8 @@ class SecretShare(object):
         vb = field.vec_bytes(n)
         if out is None:  # pooled chunked block (memory.py: the split's fast placement)
             out = memory.share_block((max(shares, 0), vb), dev)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (shares, vb) or not out.is_contiguous()
-              or out.device != dev):
-            raise ValueError(f"make_shares_vec: out must be contiguous uint8 [{shares}, {vb}] on {dev}")
+        else:
+            _args.check_share_out("make_shares_vec", out, shares, vb, dev)
         if (coeffs is None and t > 1 and n > 0 and shares > 0 and _native.mt_compatible(self.random)
                 and _native.mt_split_device(self.random, vals, out, n, t, shares)):
             # fused: the reference's MT19937 draws feed the split in registers (no coefficient block)
@@ -400,10 +396,7 @@ class SecretShare(object):
         self._require_m521()
         import torch
 
-        if self.threshold > shares:
-            raise ValueError("threshold should be little equal than shares")
-        if shares > _native.MAX_SHARES or self.threshold > _native.MAX_THRESHOLD:
-            raise NotImplementedError("make_shares_vec_many: at most 65535 shares and threshold 64")
+        _args.check_limits("make_shares_vec_many", self.threshold, shares, _native.MAX_SHARES, _native.MAX_THRESHOLD)
         dev = _device()
         vals = [_device_values(x, dev, "make_shares_vec_many") for x in tensors]
         ns = [v.numel() for v in vals]
@@ -424,8 +417,8 @@ class SecretShare(object):
                 raise ValueError(f"make_shares_vec_many: {len(outs)} outs for {len(vals)} tensors")
             for out, vb in zip(outs, vbs):
                 if (out.dtype != torch.uint8 or tuple(out.shape) != (shares, vb) or not out.is_contiguous()
-                        or out.device != dev):
-                    raise ValueError(f"make_shares_vec_many: out must be contiguous uint8 [{shares}, {vb}] on {dev}")
+                        or out.device != dev):  # (inline: no call per tensor)
+                    _args.check_share_out("make_shares_vec_many", out, shares, vb, dev)
             ptrs = [out.data_ptr() for out in outs]
         if (t in (2, 3, 5) and shares > 0 and sum(ns) > 0 and _native.mt_compatible(self.random)
                 and _native.mt_split_many_device(self.random, _concat_values(vals), list(zip(ns, ptrs)), t, shares)):
@@ -451,10 +444,7 @@ class SecretShare(object):
 
         import torch
 
-        if self.threshold > shares:
-            raise ValueError("threshold should be little equal than shares")
-        if shares > _native.MAX_SHARES or self.threshold > 8:
-            raise NotImplementedError("make_shares_vec_prng: at most 65535 shares and threshold 8")
+        _args.check_limits("make_shares_vec_prng", self.threshold, shares, _native.MAX_SHARES, 8)
         if key is None:
             key = _secrets.token_bytes(32)
         dev = _device()
@@ -463,9 +453,8 @@ class SecretShare(object):
         vb = field.vec_bytes(n)
         if out is None:
             out = memory.share_block((max(shares, 0), vb), dev)
-        elif (out.dtype != torch.uint8 or tuple(out.shape) != (shares, vb) or not out.is_contiguous()
-              or out.device != dev):
-            raise ValueError(f"make_shares_vec_prng: out must be contiguous uint8 [{shares}, {vb}] on {dev}")
+        else:
+            _args.check_share_out("make_shares_vec_prng", out, shares, vb, dev)
         if shares > 0:
             if self.threshold <= 1:
                 _native.split_u64(vals, None, out, n, 1, shares)
@@ -487,33 +476,20 @@ class SecretShare(object):
         self._require_m521()
         import torch
 
-        vecs = list(shares.unbind(0)) if isinstance(shares, torch.Tensor) and shares.dim() == 2 else list(shares)
+        vecs = _args.rows_of(shares)
         xs = [int(x) for x in xs]
         if len(vecs) != len(xs):
             raise ValueError("resolve_shares_vec: one abscissa per share vector")
-        if len(xs) == 0:
-            raise ValueError("not enough values to unpack (expected 2, got 0)")
-        k = len(xs)
-        if k < self.threshold:
-            raise ValueError("need at least {} shares".format(self.threshold))
-        if k != len(set(xs)):
-            raise ValueError("shares must be distinct")
-        if k == 1:
-            raise TypeError("reduce() of empty iterable with no initial value")
+        self._check_abscissas(xs)
         dev = _device()
         vb = field.vec_bytes(n)
         for v in vecs:
             if v.dtype != torch.uint8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
                 raise ValueError(f"resolve_shares_vec: share vectors must be contiguous uint8 [{vb}] on {dev}")
         over = torch.zeros(1, dtype=torch.int32, device=dev) if return_overflow else None
-        if out == "int64":
-            res = torch.empty(n, dtype=torch.int64, device=dev)
-            _resolve_vectors(vecs, xs, n, self.threshold, out_u64=res, overflow=over)
-        elif out == "field":
-            res = torch.empty(vb, dtype=torch.uint8, device=dev)
-            _resolve_vectors(vecs, xs, n, self.threshold, out_fe=res, overflow=over)
-        else:
-            raise ValueError('resolve_shares_vec: out must be "int64" or "field"')
+        _args.check_out_form("resolve_shares_vec", out)
+        res, out_fe, out_u64 = _args.result(out, n, vb, dev)
+        _resolve_vectors(vecs, xs, n, self.threshold, out_fe=out_fe, out_u64=out_u64, overflow=over)
         return (res, over) if return_overflow else res
 
     def resolve_records_vec(self, records, xs: Optional[Sequence[int]], n: int, *, out: str = "int64",
@@ -554,9 +530,8 @@ class SecretShare(object):
 
         from . import codec
 
-        recs = [tuple(r) for r in records]
-        if any(len(r) != 2 for r in recs):
-            raise ValueError("resolve_records_vec: records must be (packed, offsets) pairs")
+        what = "resolve_records_vec"
+        recs = _args.wire_pairs(what, records)
         if xs is not None:
             xs = [int(x) for x in xs]
             if len(recs) != len(xs):
@@ -564,63 +539,38 @@ class SecretShare(object):
             self._check_abscissas(xs)
         elif not recs:
             raise ValueError("not enough values to unpack (expected 2, got 0)")
-        if out not in ("int64", "field"):
-            raise ValueError('resolve_records_vec: out must be "int64" or "field"')
+        _args.check_out_form(what, out)
         n = int(n)
         if n < 0:
             raise ValueError("resolve_records_vec: n must not be negative")
-        first = recs[0][0]
-        for packed, offsets in recs:
-            if not (isinstance(packed, torch.Tensor) and packed.dtype == torch.uint8 and packed.dim() == 1
-                    and packed.is_contiguous()):
-                raise ValueError("resolve_records_vec: packed records must be contiguous 1-D uint8 tensors")
-            if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1
-                    and offsets.is_contiguous()):
-                raise ValueError("resolve_records_vec: offsets must be contiguous 1-D int64 tensors")
-            if packed.device != first.device or offsets.device != first.device:
-                raise ValueError("resolve_records_vec: every wire's records and offsets must be on one device")
-            if offsets.numel() < n + 1:
-                raise ValueError(f"resolve_records_vec: offsets must hold n + 1 = {n + 1} entries, "
-                                 f"got {offsets.numel()}")
-        if bad is not None and not (isinstance(bad, torch.Tensor) and bad.dtype == torch.int32
-                                    and tuple(bad.shape) == (2,) and bad.is_contiguous()
-                                    and bad.device == first.device):
-            raise ValueError("resolve_records_vec: bad must be a contiguous int32 tensor [2] on the records' device")
+        first = _args.check_wires(what, recs, n)
+        _args.check_bad_flag(what, bad, first, "records")
         if xs is None and n == 0:
             raise ValueError("resolve_records_vec: xs=None needs a first record to read each abscissa from")
         dev = _device()
-        if first.device != dev:
+        if first != dev:
             raise ValueError(f"resolve_records_vec: records must be on {dev}")
         if xs is None:
             xs = _first_record_xs(recs)
             self._check_abscissas(xs)
         k = len(xs)
-        checked = bad is None
-        if checked:
-            bad = torch.zeros(2, dtype=torch.int32, device=dev)
-        vb = field.vec_bytes(n)
+        bad, checked = _args.bad_flag(bad, dev)
         over = torch.zeros(1, dtype=torch.int32, device=dev) if return_overflow else None
-        as_int = out == "int64"
-        res = (torch.empty(n, dtype=torch.int64, device=dev) if as_int
-               else torch.empty(vb, dtype=torch.uint8, device=dev))
-        if k <= _native.MAX_RESOLVE and all(0 <= x < (1 << 64) for x in xs):
-            # the kernels load dwords: one aligned device copy of a misaligned view
-            recs = [(p.clone() if p.data_ptr() & 3 else p, o) for p, o in recs]
+        res, out_fe, out_u64 = _args.result(out, n, field.vec_bytes(n), dev)
+        if k <= _native.MAX_RESOLVE and all(_args.fits_u64(x) for x in xs):
+            recs, wires = _args.aligned_wires(recs)
             w = _native.lagrange(xs, self.threshold)
-            _native.reconstruct_records([(p.data_ptr(), p.numel(), o.data_ptr()) for p, o in recs], xs, w, bad,
-                                        out_fe=None if as_int else res, out_u64=res if as_int else None,
-                                        overflow=over, n=n)
+            _native.reconstruct_records(wires, xs, w, bad, out_fe=out_fe, out_u64=out_u64, overflow=over, n=n)
         else:  # decode every wire, then the grouped full-width interpolation: the same results
             vecs = []
             for (p, o), x in zip(recs, xs):
                 v, got = codec.decode_share_vec(p, o, n, bad=bad[0:1])
-                if 0 <= x < (1 << 64):  # (a record's x is 64 bits at most: a larger abscissa never matches)
+                if _args.fits_u64(x):  # (a record's x is 64 bits at most: a larger abscissa never matches)
                     bad[1:2] += (got != _i64(x)).sum().to(torch.int32)
                 else:
                     bad[1:2] += n
                 vecs.append(v)
-            _resolve_vectors(vecs, xs, n, self.threshold, out_fe=None if as_int else res,
-                             out_u64=res if as_int else None, overflow=over)
+            _resolve_vectors(vecs, xs, n, self.threshold, out_fe=out_fe, out_u64=out_u64, overflow=over)
         if checked:
             codec.check_bad_records(bad)
         return (res, over) if return_overflow else res
@@ -670,16 +620,8 @@ class SecretShare(object):
         for sh in shares:
             if (sh.shape[0] if isinstance(sh, torch.Tensor) and sh.dim() == 2 else len(sh)) != k:
                 raise ValueError("resolve_shares_vec: one abscissa per share vector")
-        if k == 0:
-            raise ValueError("not enough values to unpack (expected 2, got 0)")
-        if k < self.threshold:
-            raise ValueError("need at least {} shares".format(self.threshold))
-        if k != len(set(xs)):
-            raise ValueError("shares must be distinct")
-        if k == 1:
-            raise TypeError("reduce() of empty iterable with no initial value")
-        if out not in ("int64", "field"):
-            raise ValueError('resolve_shares_vec_many: out must be "int64" or "field"')
+        self._check_abscissas(xs)
+        _args.check_out_form("resolve_shares_vec_many", out)
         dev = _device()
         vbs = [field.vec_bytes(n) for n in ns]
         u8 = torch.uint8
@@ -714,15 +656,14 @@ class SecretShare(object):
                     raise ValueError(f"resolve_shares_vec_many: out must be contiguous {out} [{sz}] on {dev}")
             optrs = [o.data_ptr() for o in outs]
         over = torch.zeros(len(ns), dtype=torch.int32, device=dev) if return_overflow else None
-        if k <= _native.MAX_RESOLVE and all(0 <= x < (1 << 64) for x in xs):
+        if k <= _native.MAX_RESOLVE and all(_args.fits_u64(x) for x in xs):
             if ns:
                 w = _native.lagrange(xs, self.threshold)
                 _native.reconstruct_many(ns, rows, w, dev, out_fe_ptrs=None if as_int else optrs,
                                          out_u64_ptrs=optrs if as_int else None, overflow=over)
         else:  # the calls this one stands for, into the same outputs
             for j, (sh, n, o) in enumerate(zip(shares, ns, outs)):
-                vecs = list(sh.unbind(0)) if isinstance(sh, torch.Tensor) and sh.dim() == 2 else list(sh)
-                _resolve_vectors(vecs, xs, n, self.threshold, out_fe=None if as_int else o,
+                _resolve_vectors(_args.rows_of(sh), xs, n, self.threshold, out_fe=None if as_int else o,
                                  out_u64=o if as_int else None, overflow=None if over is None else over[j:j + 1])
         return (outs, over) if return_overflow else outs
 
@@ -768,14 +709,7 @@ class SecretShare(object):
         if first.numel() % field.TILE_BYTES:
             raise ValueError(f"sum_shares_vec: blocks must be whole {field.TILE_BYTES}-byte tiles, "
                              f"got {first.numel()} bytes")
-        negate = None
-        if signs is not None:
-            signs = list(signs)
-            if len(signs) != len(blocks):
-                raise ValueError(f"sum_shares_vec: {len(signs)} signs for {len(blocks)} blocks")
-            if any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s not in (1, -1) for s in signs):
-                raise ValueError("sum_shares_vec: signs must be +1 or -1")
-            negate = [s < 0 for s in signs]
+        negate = _args.negate_flags("sum_shares_vec", signs, len(blocks), "blocks")
         if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8
                                 or out.shape != first.shape or out.device != first.device
                                 or not out.is_contiguous()):
@@ -839,54 +773,30 @@ class SecretShare(object):
         from . import codec
 
         what = "sum_records_vec"
-        recs = [tuple(r) for r in records]
-        if any(len(r) != 2 for r in recs):
-            raise ValueError(f"{what}: records must be (packed, offsets) pairs")
+        recs = _args.wire_pairs(what, records)
         if not recs:
             raise ValueError(f"{what}: no records")
         n = int(n)
         if n < 0:
             raise ValueError(f"{what}: n must not be negative")
-        first = recs[0][0]
-        for packed, offsets in recs:
-            if not (isinstance(packed, torch.Tensor) and packed.dtype == torch.uint8 and packed.dim() == 1
-                    and packed.is_contiguous()):
-                raise ValueError(f"{what}: packed records must be contiguous 1-D uint8 tensors")
-            if not (isinstance(offsets, torch.Tensor) and offsets.dtype == torch.int64 and offsets.dim() == 1
-                    and offsets.is_contiguous()):
-                raise ValueError(f"{what}: offsets must be contiguous 1-D int64 tensors")
-            if packed.device != first.device or offsets.device != first.device:
-                raise ValueError(f"{what}: every wire's records and offsets must be on one device")
-            if offsets.numel() < n + 1:
-                raise ValueError(f"{what}: offsets must hold n + 1 = {n + 1} entries, got {offsets.numel()}")
+        first = _args.check_wires(what, recs, n)
         if x is not None:
             if isinstance(x, bool) or not isinstance(x, numbers.Integral):
                 raise ValueError(f"{what}: x must be an integer or None")
             x = int(x)
-            if not 0 <= x < (1 << 64):
+            if not _args.fits_u64(x):
                 raise ValueError(f"{what}: x must fit 64 bits")
         elif n == 0:
             raise ValueError(f"{what}: x=None needs a first record to read the abscissa from")
-        negate = None
-        if signs is not None:
-            signs = list(signs)
-            if len(signs) != len(recs):
-                raise ValueError(f"{what}: {len(signs)} signs for {len(recs)} wires")
-            if any(isinstance(s, bool) or not isinstance(s, numbers.Integral) or s not in (1, -1) for s in signs):
-                raise ValueError(f"{what}: signs must be +1 or -1")
-            negate = [s < 0 for s in signs]
+        negate = _args.negate_flags(what, signs, len(recs), "wires")
         vb = field.vec_bytes(n)
         for name, t in (("acc", acc), ("out", out)):
             if t is not None and not (isinstance(t, torch.Tensor) and t.dtype == torch.uint8
-                                      and tuple(t.shape) == (vb,) and t.is_contiguous()
-                                      and t.device == first.device):
+                                      and tuple(t.shape) == (vb,) and t.is_contiguous() and t.device == first):
                 raise ValueError(f"{what}: {name} must be a contiguous uint8 tensor [{vb}] on the records' device")
-        if bad is not None and not (isinstance(bad, torch.Tensor) and bad.dtype == torch.int32
-                                    and tuple(bad.shape) == (2,) and bad.is_contiguous()
-                                    and bad.device == first.device):
-            raise ValueError(f"{what}: bad must be a contiguous int32 tensor [2] on the records' device")
+        _args.check_bad_flag(what, bad, first, "records")
         dev = _device()
-        if first.device != dev:
+        if first != dev:
             raise ValueError(f"{what}: records must be on {dev}")
         if x is None:
             got = _first_record_xs(recs, what)
@@ -897,13 +807,9 @@ class SecretShare(object):
             out = torch.empty(vb, dtype=torch.uint8, device=dev)
         if n == 0:
             return out
-        checked = bad is None
-        if checked:
-            bad = torch.zeros(2, dtype=torch.int32, device=dev)
-        # the kernel loads dwords: one aligned device copy of a misaligned view
-        recs = [(p.clone() if p.data_ptr() & 3 else p, o) for p, o in recs]
-        _native.sum_records([(p.data_ptr(), p.numel(), o.data_ptr()) for p, o in recs], x, negate, bad, out, acc=acc,
-                            n=n)
+        bad, checked = _args.bad_flag(bad, dev)
+        recs, wires = _args.aligned_wires(recs)
+        _native.sum_records(wires, x, negate, bad, out, acc=acc, n=n)
         if checked:
             codec.check_bad_records(bad, what=what)
         return out

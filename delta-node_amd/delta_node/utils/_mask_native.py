@@ -7,10 +7,6 @@ from typing import List, Optional, Sequence, Union
 from ..crypto.shamir import _native
 
 MAX_GENS = 16
-EXPORTS = ("dn_pcg64_seed", "dn_pcg64_advance", "dn_bounded_i64_accumulate", "dn_bounded_i64_rejects",
-           "dn_unfix_precision", "dn_i64_sum")
-
-
 class PCG64(ctypes.Structure):
     """Mirror of dn_pcg64_t (numpy PCG64 state: 128-bit state and increment)."""
 
@@ -26,26 +22,23 @@ class PCG64(ctypes.Structure):
         return (self.inc_hi << 64) | self.inc_lo
 
 
+vp, u64, i32, i64 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int64
+_SYMBOLS = {  # name -> (restype, argtypes, required), as _native._SYMBOLS
+    "dn_pcg64_seed": (i32, [ctypes.POINTER(ctypes.c_uint32), i32, ctypes.POINTER(PCG64)], True),
+    "dn_pcg64_advance": (i32, [ctypes.POINTER(PCG64), u64], True),
+    "dn_bounded_i64_accumulate": (i32, [ctypes.POINTER(PCG64), ctypes.POINTER(ctypes.c_int32),
+                                        ctypes.POINTER(ctypes.c_uint64), i32, i64, u64, vp, vp, i32, vp, u64, u64, vp,
+                                        vp], True),
+    "dn_bounded_i64_rejects": (i32, [ctypes.POINTER(PCG64), u64, u64, u64, vp, vp, ctypes.c_uint32, vp], True),
+    "dn_unfix_precision": (i32, [vp, vp, u64, i32, vp], True),
+    "dn_i64_sum": (i32, [ctypes.POINTER(vp), i32, vp, u64, vp], True),
+}
+EXPORTS = tuple(_SYMBOLS)
+
+
 def lib() -> ctypes.CDLL:
-    L = _native.lib()
-    if not getattr(L, "_dn_mask_bound", False):  # argtypes, once per loaded library
-        vp, u64, i32, i64 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int64
-        L.dn_pcg64_seed.restype = i32
-        L.dn_pcg64_seed.argtypes = [ctypes.POINTER(ctypes.c_uint32), i32, ctypes.POINTER(PCG64)]
-        L.dn_pcg64_advance.restype = i32
-        L.dn_pcg64_advance.argtypes = [ctypes.POINTER(PCG64), u64]
-        L.dn_bounded_i64_accumulate.restype = i32
-        L.dn_bounded_i64_accumulate.argtypes = [ctypes.POINTER(PCG64), ctypes.POINTER(ctypes.c_int32),
-                                                ctypes.POINTER(ctypes.c_uint64), i32, i64, u64, vp, vp, i32, vp,
-                                                u64, u64, vp, vp]
-        L.dn_bounded_i64_rejects.restype = i32
-        L.dn_bounded_i64_rejects.argtypes = [ctypes.POINTER(PCG64), u64, u64, u64, vp, vp, ctypes.c_uint32, vp]
-        L.dn_i64_sum.restype = i32
-        L.dn_i64_sum.argtypes = [ctypes.POINTER(vp), i32, vp, u64, vp]
-        L.dn_unfix_precision.restype = i32
-        L.dn_unfix_precision.argtypes = [vp, vp, u64, i32, vp]
-        L._dn_mask_bound = True
-    return L
+    L = _native.lib()  # (the flag is looked at here: no further call once the library is bound)
+    return L if getattr(L, "_dn_mask_bound", False) else _native.bind(L, _SYMBOLS, "_dn_mask_bound")
 
 
 def entropy_words(seed: Union[int, bytes, Sequence[int]]) -> List[int]:

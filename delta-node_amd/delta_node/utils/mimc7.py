@@ -25,24 +25,21 @@ __all__ = ["calc_weight_commitment", "calc_data_commitment"]
 
 Q = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 DATA_BLOCK = 128
-EXPORTS = ("dn_mimc7_data_rows", "dn_mimc7_merkle_blocks", "dn_mimc7_weight_chain", "dn_mimc7_hash",
-           "dn_mimc7_weight_commitment_host", "dn_mimc7_params")
+vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
+_SYMBOLS = {  # name -> (restype, argtypes, required), as _native._SYMBOLS
+    "dn_mimc7_data_rows": (i32, [vp, u64, i32, vp, vp, vp], True),
+    "dn_mimc7_merkle_blocks": (i32, [vp, u64, vp, vp], True),
+    "dn_mimc7_weight_chain": (i32, [vp, u64, i32, vp, vp, vp], True),
+    "dn_mimc7_hash": (i32, [vp, vp, u64, vp, vp], True),
+    "dn_mimc7_weight_commitment_host": (i32, [vp, u64, i32, vp], True),
+    "dn_mimc7_params": (i32, [vp, vp], True),
+}
+EXPORTS = tuple(_SYMBOLS)
+
+
 def _lib():
-    L = _native.lib()
-    if not getattr(L, "_dn_mimc7_bound", False):  # argtypes, once per loaded library
-        vp, u64, i32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int
-        L.dn_mimc7_data_rows.restype = i32
-        L.dn_mimc7_data_rows.argtypes = [vp, u64, i32, vp, vp, vp]
-        L.dn_mimc7_merkle_blocks.restype = i32
-        L.dn_mimc7_merkle_blocks.argtypes = [vp, u64, vp, vp]
-        L.dn_mimc7_weight_chain.restype = i32
-        L.dn_mimc7_weight_chain.argtypes = [vp, u64, i32, vp, vp, vp]
-        L.dn_mimc7_hash.restype = i32
-        L.dn_mimc7_hash.argtypes = [vp, vp, u64, vp, vp]
-        L.dn_mimc7_weight_commitment_host.restype = i32
-        L.dn_mimc7_weight_commitment_host.argtypes = [vp, u64, i32, vp]
-        L._dn_mimc7_bound = True
-    return L
+    L = _native.lib()  # (the flag is looked at here: no further call once the library is bound)
+    return L if getattr(L, "_dn_mimc7_bound", False) else _native.bind(L, _SYMBOLS, "_dn_mimc7_bound")
 
 
 def _limbs_to_int(row) -> int:
