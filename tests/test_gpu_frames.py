@@ -320,7 +320,9 @@ def _corrupt(frame, pos: int, value: int):
                                            ("truncated", [1, 1])])
 def test_one_corrupted_field_at_a_time(kind, want_bad):
     """The offsets are min(cumsum, frame_bytes - R(n)) whatever the bytes say,
-    and `bad` holds the two counts.  (These offsets go to no other kernel.)"""
+    and `bad` holds the two counts.  (These offsets go to no other kernel here:
+    test_gpu_record_edges.py's test_corrupt_frames_open_to_offsets_the_record_kernels_can_take
+    hands the offsets of such frames to sum_records_vec and resolve_records_vec.)"""
     n, x = B + 300, 5
     lens = random_lens(n, 4242)
     lens[10] = 100  # so that +-1 stays a u8
