@@ -392,7 +392,8 @@ class SecretShare(object):
         338 B of share traffic at 3-of-5).  Where the fused form does not
         apply (a generator that is not plain MT19937, t not in {2, 3, 5}, a
         stream beyond the jump table, a rejected draw) the per-tensor
-        make_shares_vec loop runs into the same outputs."""
+        make_shares_vec loop runs into the same outputs, and
+        `self.last_draw_rejected` reports a redraw in any of the tensors."""
         self._require_m521()
         import torch
 
@@ -424,8 +425,11 @@ class SecretShare(object):
                 and _native.mt_split_many_device(self.random, _concat_values(vals), list(zip(ns, ptrs)), t, shares)):
             self.last_draw_rejected = False
             return outs
+        rejected = self.last_draw_rejected = False
         for v, out in zip(vals, outs):  # the calls this one stands for, into the same outputs
             self.make_shares_vec(v, shares, out=out)
+            rejected = rejected or self.last_draw_rejected
+        self.last_draw_rejected = rejected  # a redraw in any tensor, not only in the last one
         return outs
 
     def make_shares_vec_prng(self, values, shares: int, *, key: Optional[bytes] = None, nonce: int = 0,

@@ -123,6 +123,9 @@ def test_native_mt_coefficients_match_reference(key):
 
 
 def test_native_mt_mid_stream_and_rejection_free_path():
+    """The host draw from a mid-array start on a seeded generator, which never
+    redraws; the rejection path (raw draws >= p - 1 on crafted states) is
+    test_mt_edges_host.py's."""
     r = random.Random(77)
     r.getrandbits(32 * 100)  # start mid-buffer (index != 624)
     r.random()
