@@ -20,6 +20,7 @@ copy with numpy alone.
 from __future__ import annotations
 
 import ctypes
+import threading
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 from . import _args, _native, field
@@ -48,20 +49,50 @@ def _lib():
     return L if getattr(L, "_dn_codec_bound", False) else _native.bind(L, _SYMBOLS, "_dn_codec_bound")
 
 
-_scratch_cache = {}  # (device index, stream) -> uint8 scratch tensor (grown on demand)
+_tls = threading.local()  # per thread: .scratch, .flags (dicts keyed by (device index, stream))
+
+
+def _cache(name: str) -> dict:
+    cache = getattr(_tls, name, None)
+    if cache is None:
+        cache = {}
+        setattr(_tls, name, cache)
+    return cache
 
 
 def _scratch(dev, nbytes: int):
-    """Encoder scratch, cached per device and stream (the kernels of one stream
-    run in order, so one buffer serves every call queued on it)."""
+    """Encoder scratch, cached per thread, device and stream (grown on demand).
+    The kernels of one stream run in order, so one buffer serves every call
+    that ONE thread queues on it: a call's launches are queued back to back
+    before the thread's next call starts.  Two threads on one stream are not
+    ordered against each other — the entry points are entered with the GIL
+    released, so their launches interleave — and a buffer they shared would
+    carry one call's lengths, table or totals into the other's launches.
+    Hence the thread in the key, as `_native._mt_scratch`."""
     import torch
 
+    cache = _cache("scratch")
     key = (dev.index, _native.stream_ptr())
-    buf = _scratch_cache.get(key)
+    buf = cache.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-        _scratch_cache[key] = buf
+        cache[key] = buf = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
     return buf
+
+
+def _checked_flag(dev):
+    """The zeroed int32 bad-record counter of decode_share_vec's checked form,
+    cached per thread, device and stream: the call zeroes it, launches and
+    reads it back, and another thread's zero or count must not fall between."""
+    import torch
+
+    cache = _cache("flags")
+    key = (dev.index, _native.stream_ptr())
+    bad = cache.get(key)
+    if bad is None:
+        bad = cache[key] = torch.zeros(1, dtype=torch.int32, device=dev)
+    else:
+        bad.zero_()
+    return bad
 
 
 def _out(t, numel: int, dtype, dev, what: str):
@@ -276,9 +307,6 @@ def encoded_capacity(n: int, x: int) -> int:
     return int(_lib().dn_m521_encoded_capacity(n, x))
 
 
-_flags = {}  # (device index, stream) -> int32 bad-record counter of the checked form
-
-
 def decode_share_vec(packed, offsets, n: int, *, out=None, xs=None, bad=None):
     """(packed, offsets[n+1]) -> (tiled uint8 vector of y mod p, uint64 xs as int64 tensor).
 
@@ -299,12 +327,7 @@ def decode_share_vec(packed, offsets, n: int, *, out=None, xs=None, bad=None):
     xs = _out(xs, max(n, 1), torch.int64, dev, "decode_share_vec xs")
     checked = bad is None
     if checked:
-        key = (dev.index, _native.stream_ptr())
-        bad = _flags.get(key)
-        if bad is None:
-            bad = _flags[key] = torch.zeros(1, dtype=torch.int32, device=dev)
-        else:
-            bad.zero_()
+        bad = _checked_flag(dev)
     elif not (isinstance(bad, torch.Tensor) and bad.dtype == torch.int32 and bad.device == dev):
         raise ValueError("decode_share_vec: bad must be an int32 tensor on the packed records' device")
     _native.check(L.dn_m521_decode_shares(packed.data_ptr(), packed.numel(), offsets.data_ptr(), n, vec.data_ptr(),

@@ -519,7 +519,10 @@ class SecretShare(object):
                  y > 68 bytes, offsets decreasing or past the wire) or carries
                  an x other than its wire's.  An int32 device tensor [2]: the
                  two counts are ADDED to it on the device and the call does not
-                 synchronise; `codec.check_bad_records(bad)` raises later
+                 synchronise; `codec.check_bad_records(bad)` raises later.
+                 This form (with xs given) can be captured into a graph; there
+                 is no out= tensor, so the result is then allocated from the
+                 graph's pool and rewritten by every replay
         Same checks, messages and exception types as `resolve_shares_vec`, all
         before any device use.  The results are those of decode_share_vec on
         every wire followed by resolve_shares_vec, bit for bit (an
