@@ -16,6 +16,10 @@ the offsets reach the receiver: `encode_share_frame` / `encode_frames_many`
 encode straight into frames, `open_frames` turns received frames back into
 (packed, offsets) with one validated scan, `frame_fields_host` parses a host
 copy with numpy alone.
+
+`commit_records_vec` / `verify_records_vec` are the commitment step of the
+same path: SHA-256 of every record (the reference's `calc_commitment` per
+share), computed or checked on the device in one launch.
 """
 from __future__ import annotations
 
@@ -40,6 +44,8 @@ _SYMBOLS = {  # name -> (restype, argtypes, required), as _native._SYMBOLS
     "dn_m521_frame_finish": (i32, [pvp, pvp, pu64, u64, u64, vp], False),
     "dn_m521_frame_scratch_bytes": (u64, [u64, u64], False),
     "dn_m521_frame_open": (i32, [pvp, pu64, pu64, u64, u64, pvp, vp, vp, u64, vp], False),
+    "dn_sha256_commit_records": (i32, [vp, u64, vp, u64, vp, vp, vp], False),
+    "dn_sha256_verify_records": (i32, [vp, u64, vp, u64, vp, vp, vp, vp], False),
 }
 EXPORTS = tuple(_SYMBOLS)
 
@@ -361,6 +367,141 @@ def records_to_list(packed_host, offsets_host) -> List[bytes]:
     buf = bytes(packed_host.numpy() if hasattr(packed_host, "numpy") else packed_host)
     off = offsets_host.tolist()
     return [buf[off[i]:off[i + 1]] for i in range(len(off) - 1)]
+
+
+# ------------------------------------------------------------------ share commitments
+# utils.calc_commitment (utils/commitment.py:5-12) of every record of a wire,
+# as the reference's runner computes it per share before sealing it
+# (runner/horizontal/agg.py:160-162) and checks it on receipt
+# (runner/horizontal/agg.py:257-272, coord/horizontal/agg.py:309-318, 342-348).
+DIGEST_BYTES = 32
+
+
+def _commit_args(what: str, packed, offsets, n: int, bad):
+    """The wire and the flag of commit_records_vec / verify_records_vec, no device use: (n, the wire's device)."""
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"{what}: n must not be negative")
+    dev = _args.check_wires(what, [(packed, offsets)], n)
+    _args.check_bad_flag(what, bad, dev, "records")
+    return n, dev
+
+
+def _overlaps(a, b) -> bool:
+    a0, b0 = a.data_ptr(), b.data_ptr()
+    return a.numel() > 0 and b.numel() > 0 and a0 < b0 + b.numel() * b.element_size() \
+        and b0 < a0 + a.numel() * a.element_size()
+
+
+def _commit_device(what: str, dev):
+    got = _native.require_device()
+    if dev != got:
+        raise ValueError(f"{what}: records must be on {got}")
+    return got
+
+
+def commit_records_vec(packed, offsets, n: int, *, out=None, bad=None):
+    """SHA-256 of every record of a wire -> uint8 device tensor [n, 32]: row e
+    is `utils.calc_commitment(packed[offsets[e]:offsets[e + 1]])`, bit for bit,
+    in one launch (dn_sha256_commit_records) — the commitments of
+    `upload_secret_shares` for a whole share vector, between the encode and
+    `aes.encrypt_vec`.
+
+    packed, offsets  a wire as `encode_share_vec` / `encode_shares_many` return
+             it, or the record view frame[R(n):] of a frame with its offsets
+             (on the sender's side, or out of `open_frames`): contiguous 1-D
+             uint8 / int64 device tensors, n + 1 offsets.  A `packed` view that
+             is not 4-byte aligned is copied once
+    out      optional contiguous uint8 device tensor of >= 32 n bytes, 4-byte
+             aligned (a 16-byte aligned one is stored as 16-byte words), not
+             overlapping `packed`; bytes past 32 n are left alone
+    bad      None: one read-back after the launch, and ValueError naming the
+             count of records whose offsets leave their window (decreasing,
+             below their wave's first offset, past its last or past `packed`).
+             An int32 device tensor [2]: that count is ADDED to bad[0] and the
+             call does not synchronise; such a record's digest is 32 zero
+             bytes; `check_bad_commit(bad, what="commit_records_vec")` raises later
+    An empty record is hashed as b"".  Argument errors are raised before any
+    device use; n = 0 returns an empty [0, 32] tensor."""
+    import torch
+
+    what = "commit_records_vec"
+    n, first = _commit_args(what, packed, offsets, n, bad)
+    if out is not None:
+        out = _wire_out(out, DIGEST_BYTES * n, first, f"{what} out")
+        if _overlaps(out, packed):
+            raise ValueError(f"{what}: out overlaps packed")
+    dev = _commit_device(what, first)
+    if out is None:
+        out = torch.empty(DIGEST_BYTES * n, dtype=torch.uint8, device=dev)
+    res = out.view(-1)[: DIGEST_BYTES * n].view(n, DIGEST_BYTES)
+    if n == 0:
+        return res
+    L = _native.need(_lib(), "dn_sha256_commit_records")
+    bad, checked = _args.bad_flag(bad, dev)
+    recs, ((p, nbytes, o),) = _args.aligned_wires([(packed, offsets)])
+    _native.check(L.dn_sha256_commit_records(p, nbytes, o, n, out.data_ptr(), bad.data_ptr(), _native.stream_ptr()))
+    if checked:
+        check_bad_commit(bad, what=what)
+    return res
+
+
+def verify_records_vec(packed, offsets, n: int, commitments, *, ok=None, bad=None) -> None:
+    """Check every record of a wire against its commitment, in one launch
+    (dn_sha256_verify_records): record e passes if
+    `commitments[e] == utils.calc_commitment(packed[offsets[e]:offsets[e + 1]])`
+    — the check of `get_secret_shares` and of the coordinator for a whole
+    share vector, between `open_frames` and `resolve_records_vec` /
+    `sum_records_vec`.
+
+    packed, offsets  as in `commit_records_vec`
+    commitments  contiguous uint8 tensor on the wire's device holding 32 n
+             bytes, as [n, 32] (what commit_records_vec returns) or flat
+    ok       optional contiguous uint8 device tensor of >= n entries, not
+             overlapping `packed`: ok[e] = 1 where record e passes, else 0
+    bad      None: one read-back after the launch, and ValueError naming the
+             records whose offsets leave their window and the records whose
+             SHA-256 is not their commitment (where the reference drops the
+             share).  An int32 device tensor [2]: the two counts are ADDED to
+             it and the call does not synchronise;
+             `check_bad_commit(bad)` raises later
+    Argument errors are raised before any device use."""
+    import torch
+
+    what = "verify_records_vec"
+    n, first = _commit_args(what, packed, offsets, n, bad)
+    c = commitments
+    if not (isinstance(c, torch.Tensor) and c.dtype == torch.uint8 and c.is_contiguous() and c.device == first
+            and tuple(c.shape) in ((n, DIGEST_BYTES), (DIGEST_BYTES * n,))):
+        raise ValueError(f"{what}: commitments must be a contiguous uint8 tensor [{n}, {DIGEST_BYTES}] or "
+                         f"[{DIGEST_BYTES * n}] on the records' device")
+    if ok is not None:
+        ok = _out(ok, n, torch.uint8, first, f"{what} ok")
+        if _overlaps(ok, packed):
+            raise ValueError(f"{what}: ok overlaps packed")
+    dev = _commit_device(what, first)
+    if n == 0:
+        return
+    L = _native.need(_lib(), "dn_sha256_verify_records")
+    bad, checked = _args.bad_flag(bad, dev)
+    if c.data_ptr() & 3:  # the kernel loads dwords: one aligned device copy of a misaligned view
+        c = c.clone()
+    recs, ((p, nbytes, o),) = _args.aligned_wires([(packed, offsets)])
+    _native.check(L.dn_sha256_verify_records(p, nbytes, o, n, c.data_ptr(), None if ok is None else ok.data_ptr(),
+                                             bad.data_ptr(), _native.stream_ptr()))
+    if checked:
+        check_bad_commit(bad, what=what)
+
+
+def check_bad_commit(bad, what: str = "verify_records_vec") -> None:
+    """Raise if a deferred `verify_records_vec(..., bad=flag)` (or
+    `commit_records_vec`: what="commit_records_vec") met records whose offsets
+    leave their window (flag[0]) or records whose SHA-256 is not their
+    commitment (flag[1]): one read-back of the two counts."""
+    nbad, nmis = (int(c) for c in bad.tolist())
+    if nbad or nmis:
+        raise ValueError(f"{what}: {nbad} records whose offsets leave their window, "
+                         f"{nmis} records whose SHA-256 is not their commitment")
 
 
 # ------------------------------------------------------------------ wire frames
