@@ -9,6 +9,9 @@
 // source and one part (one table), part rows stay within the part-row region
 // and cover the polynomial's words [0, 312) in order.
 // Exit status 1 on any violation.
+// `mt_levels_check dump` prints instead, per query on stdin, what the builder
+// does for a substream count or a draw size (dump(), below):
+// tests/test_mt_levels_host.py compares tests/mt_levels.py with it.
 //
 // build: hipcc -O1 -std=c++17 --offload-arch=gfx950 -I../include -I../delta-node_amd/csrc mt_levels_check.hip
 #include "mt19937_device.hip"
@@ -18,7 +21,8 @@
 namespace dn { int set_error(int c, const char*, ...) { return c; } int device_cu_count() { return 256; }
 uint64_t mt_jump_words() { return 0; } uint64_t mt_jump_max_subs() { return 262145; }
 void mt_advance_window(const uint32_t*, uint64_t, uint32_t*) {}
-const uint64_t* mt_direct_rows_l14(uint64_t, uint64_t*) { return nullptr; }
+static bool g_rt_rows = false;  // dump mode: the runtime direct rows count as available
+const uint64_t* mt_direct_rows_l14(uint64_t, uint64_t*) { static const uint64_t row = 0; return g_rt_rows ? &row : nullptr; }
 bool mt_xpow_mod(uint64_t, uint64_t*) { return false; } }
 using namespace dn;
 extern "C" uint64_t dn_m521_vec_bytes(uint64_t n) { return n; }
@@ -86,7 +90,73 @@ int check(uint64_t S, int ki, int back, bool rt = false) {
   if (bad) printf("S=%llu ki=%d back=%d bad=%d\n", (unsigned long long)S, ki, back, bad);
   return bad != 0;
 }
-int main() {
+// Dump mode: the facts tests/mt_levels.py models, as the real builder has
+// them.  Queries on stdin, one per line:
+//   S <ki> <S>    mt_levels(S, ki) -> one "S" line, then one "L" line per level with jobs
+//   N <ncoef>     mt_sub_len, mt_subs, dn_mt19937_device_scratch_bytes(ncoef, 1) -> one "N" line
+// Built with -DDN_TUNING the DN_MT_BACK / DN_MT_RT knobs apply as in the
+// tuning library.  A level line: its jumps n, parts P, waves W, workgroups,
+// the most jobs of one workgroup, the part rows [lo, hi) it writes, the cut
+// list and the table rows it reads (runs first-last/step of job poly indices).
+void dump_level(int k, const Level& L) {
+  std::set<int32_t> polys;
+  std::vector<int32_t> cuts;
+  size_t real = 0, grp = 0;
+  int32_t prlo = 0x7fffffff, prhi = 0;
+  for (size_t g = 0; g < L.jobs.size(); g += L.W) {
+    size_t in = 0;
+    for (int w = 0; w < L.W; ++w) {
+      const JumpJob& j = L.jobs[g + w];
+      if (j.dst < 0) continue;
+      ++in, ++real;
+      polys.insert(j.poly);
+      const int lo = j.span & 0xffff, hi = j.span >> 16;
+      if (cuts.empty()) cuts.push_back(lo);
+      if (lo == cuts.back()) cuts.push_back(hi);
+      if (!L.comb.empty()) prlo = std::min(prlo, j.dst), prhi = std::max(prhi, j.dst + 1);
+    }
+    grp = std::max(grp, in);
+  }
+  const int P = L.comb.empty() ? 1 : L.comb[0].parts;
+  if (L.comb.empty()) prlo = prhi = 0;
+  printf("L k=%d n=%zu P=%d W=%d wgs=%zu grp=%zu prow=%d,%d cuts=", k, L.comb.empty() ? real : L.comb.size(), P, L.W,
+         L.jobs.size() / L.W, grp, prlo, prhi);
+  for (size_t i = 0; i < cuts.size(); ++i) printf("%s%d", i ? "," : "", cuts[i]);
+  printf(" polys=");
+  std::vector<int32_t> v(polys.begin(), polys.end());
+  for (size_t i = 0; i < v.size();) {
+    size_t e = i + 1;
+    const int32_t step = e < v.size() ? v[e] - v[i] : 1;
+    while (e < v.size() && v[e] - v[e - 1] == step) ++e;
+    printf("%s%d-%d/%d", i ? "," : "", v[i], v[e - 1], step);
+    i = e;
+  }
+  printf("\n");
+}
+int dump() {
+  g_rt_rows = true;
+  char q;
+  unsigned long long a, b;
+  while (scanf(" %c %llu", &q, &a) == 2) {
+    if (q == 'S') {
+      if (scanf("%llu", &b) != 1) return 2;
+      const MtHost& H = mt_levels(b, static_cast<int>(a));
+      printf("S ki=%llu S=%llu back=%d rt=%d part_rows=%llu direct_rows=%d jump_rows=%d rt_rows=%llu max_parts=%d\n", a, b, H.back,
+             H.rt ? 1 : 0, (unsigned long long)H.part_rows, kMtDirectRows, kMtJumpRows, (unsigned long long)kMtRtRows,
+             kMaxParts);
+      for (int k = 0; k < 3; ++k)
+        if (!H.lv[k].jobs.empty()) dump_level(k, H.lv[k]);
+    } else if (q == 'N') {
+      printf("N ncoef=%llu ki=%d S=%llu scratch=%llu head=%llu\n", a, mt_sub_len(a), (unsigned long long)mt_subs(a),
+             (unsigned long long)dn_mt19937_device_scratch_bytes(a, 1), (unsigned long long)kHead);
+    } else {
+      return 2;
+    }
+  }
+  return 0;
+}
+int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "dump")) return dump();
   int fails = 0;
   std::vector<uint64_t> Ss;
   for (uint64_t S = 1; S < 300; ++S) Ss.push_back(S);
