@@ -110,16 +110,20 @@ def _concat_values(vals: Sequence):
 
 def _eval_many(coeffs: Sequence[int], n_shares: int) -> List[int]:
     """y(x) = sum_j coeffs[j] x^j mod p for x = 1..n_shares, on the GPU.
-    coeffs[0] is the secret (any size; reduced mod p here)."""
+    coeffs[0] is the secret (any size; reduced mod p here).  The split takes
+    no threshold above its share count, which `_eval_at` does not know of
+    (the reference evaluates t coefficients at x = 1): with more coefficients
+    than shares, len(coeffs) rows are computed and the first n_shares kept."""
     import torch
 
     dev = _device()
     t = len(coeffs)
+    rows = max(n_shares, t)
     sec = _to_device_vecs([coeffs[0] % PRIME], dev)
     cof = _to_device_vecs(list(coeffs[1:]), dev) if t > 1 else None
-    out = torch.empty((n_shares, field.vec_bytes(1)), dtype=torch.uint8, device=dev)
-    _native.split_fe(sec, cof, out, 1, t, n_shares)
-    host = out.cpu().numpy()
+    out = torch.empty((rows, field.vec_bytes(1)), dtype=torch.uint8, device=dev)
+    _native.split_fe(sec, cof, out, 1, t, rows)
+    host = out[:n_shares].cpu().numpy()
     return [field.vec_to_ints(host[i], 1)[0] for i in range(n_shares)]
 
 
