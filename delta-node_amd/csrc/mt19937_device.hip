@@ -42,59 +42,25 @@
 
 #include "dn_internal.hpp"
 #include "m521_device.hpp"
+#include "mt_plan.hpp"
 #include "seg_plan.hpp"
 
 namespace dn {
 namespace {
 
-#include "mt19937_jump.inc"
-#include "mt19937_jump_short.inc"
-#include "mt19937_jump_direct.inc"
-
-// Substream lengths: L_k = 17 * 2^k words (2^k whole draws), k = 10, 12, 14,
-// one jump table each (rows A, C, B as in mt19937_jump.inc).  A draw of ncoef
-// coefficients uses one k for all its substreams (mt_sub_len): long
-// substreams for big draws (fewer jumps), short ones for small draws (a
-// substream's generation is one wave's sequential run: ~48 ns per draw, so
-// 2^14 draws cost ~0.8 ms whatever the vector size).
-// Index 3 (2^8 draws) serves only draws of at most 65 substreams, whose
-// windows are all one jump from the caller's (direct rows D_s, below): it has
-// no A / C / B rows.
-constexpr int kMtLens = 4;
-constexpr int kMtLenLog2[kMtLens] = {10, 12, 14, 8};
-constexpr int kMtTabLens = 3;  // lengths with A / C / B rows
+// The jump tables on the device, indexed by the job poly indices of
+// mt_plan.hpp: the A / C / B rows of the three table lengths, then (from
+// kMtDirectBase) the direct rows of the four lengths.
 __device__ const uint64_t kMtPolysDev[kMtTabLens][kMtJumpRows][kMtPolyWords] = {
     DN_MT_JUMP_POLYS_L10, DN_MT_JUMP_POLYS_L12, DN_MT_JUMP_POLYS};
-static_assert(kMtJumpL10 == 17ull << 10 && kMtJumpL12 == 17ull << 12 && kMtJumpL == 17ull << 14, "table lengths");
-// Direct rows (tools/gen_mt_jump.py --direct): D_s = x^(L - 624 + (s - 1) L),
-// W(s) = D_s(W_idx), s = 1..64, per length in kMtLenLog2's order.  A draw of
-// S <= 65 substreams takes ONE jump level from the caller's window instead of
-// A then B (one launch, one combine and one level's latency less).  Job poly
-// indices from kMtDirectBase address this table.
 __device__ const uint64_t kMtDirectDev[kMtLens][kMtDirectRows][kMtPolyWords] = {
     DN_MT_JUMP_DIRECT_L10, DN_MT_JUMP_DIRECT_L12, DN_MT_JUMP_DIRECT_L14, DN_MT_JUMP_DIRECT_L8};
-static_assert(kMtJumpL8 == 17ull << 8, "table lengths");
-constexpr int32_t kMtDirectBase = kMtTabLens * kMtJumpRows;
-// Runtime direct rows (host_gf2poly.cpp, kMtRtRows of them for L = 17 * 2^14,
-// uploaded once per device): job poly indices from kMtRtBase address them.
-constexpr int32_t kMtRtBase = kMtDirectBase + kMtLens * kMtDirectRows;
 
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
-constexpr int kMtN = 624, kMtM = 397;
+constexpr int kMtM = 397;
 constexpr uint32_t kMtA = 0x9908b0dfu, kMtUp = 0x80000000u, kMtLo = 0x7fffffffu;
-
-// table index of the substream length of a draw of ncoef coefficients:
-// 2^14 draws from 2^24 coefficients, 2^12 from 2^21, 2^10 down to 65 * 2^8
-// + 1, else 2^8 (at least ~2048 substreams for the big draws; a few hundred
-// jumps and a short generation run below; the smallest draws: at most 65
-// substreams of 2^8 draws, one direct jump level and a ~4352-word run)
-inline int mt_sub_len(uint64_t ncoef) {
-  if (ncoef <= static_cast<uint64_t>(kMtDirectRows + 1) << 8) return 3;
-  return ncoef >= (1ull << 24) ? 2 : ncoef >= (1ull << 21) ? 1 : 0;
-}
-inline uint64_t mt_sub_draws(int ki) { return 1ull << kMtLenLog2[ki]; }
 
 __host__ __device__ inline uint32_t mt_temper(uint32_t y) {
   y ^= (y >> 11);
@@ -130,40 +96,6 @@ __device__ __forceinline__ void pc_barrier() {
 }
 
 // ------------------------------------------------------------------ jumps
-#ifndef DN_JUMP_TABLE_POS
-#define DN_JUMP_TABLE_POS 1  // jump table built per stream position (1) or per table word (0; A/B builds)
-#endif
-
-struct JumpJob {
-  int32_t src, poly, dst;  // window indices (dst < 0: padding), jump-table row
-  int32_t span;            // words [lo, hi) of g this job evaluates: lo | hi << 16
-};
-
-// The runtime direct level (build_levels' rt; DN_MT_RT=0 in the tuning
-// build turns it off for A/B).
-#ifndef DN_MT_RT_DIRECT
-#define DN_MT_RT_DIRECT 1
-#endif
-
-// DN_MT_SPLIT2: the 2^24 draw's direct level in two halves; the first half's
-// generation (substreams [0, S/2), on a side stream) runs while the second
-// half's jumps do (their 85 KB tables beside the generation's rings), then the
-// second half's generation (round 6; the tuning build's env knob of the same
-// name A/Bs it).
-#ifndef DN_MT_SPLIT2
-#define DN_MT_SPLIT2 0
-#endif
-
-// A latency-bound level (few jobs: one Horner chain of ~312 steps per jump)
-// splits every jump into P parts over word ranges [lo, hi) of g.  Since
-// g(f) W = sum_k f^(64 k) g_k(f) W, part [lo, hi) evaluates
-// sum_{k in [lo, hi)} f^(64 (k - lo)) g_k(f) (f^(64 lo) W) by Horner over its
-// own words from the window 64 lo words further down W's stream, and the
-// parts' windows XOR to the jump (mt_combine_kernel).
-struct CombineJob {
-  int32_t dst, first, parts, pad;  // dst = XOR of window rows first .. first + parts - 1
-};
-
 struct JumpArgs {
   uint32_t* wins;  // window s at row s (row 0 the caller's array), the caller's window advanced idx words at row -1
   const JumpJob* jobs;
@@ -218,14 +150,6 @@ constexpr int kEVWords = 64 * 2;                      // words per chunk value v
 constexpr int kEPair = 16 * kEVWords + 2;              // 2050 words
 constexpr int kEWrap = ((5 * kEPair + 63) / 64) * 64;  // 10304 words
 constexpr int kEWords = kEWrap + 5 * kEPair;           // 82 KB
-constexpr int kJumpWaves = 16;  // at most this many jumps (waves) per workgroup, all from one source and part
-// 32: small levels (the direct level of a small draw, level A) split into
-// parts of ~10 Horner steps (make_shares_vec 2^12 -1.5 us, level A 26.5 vs
-// 29.1 us at 2^24; profiles/r04/e/)
-#ifndef DN_MT_MAX_PARTS
-#define DN_MT_MAX_PARTS 32
-#endif
-constexpr int kMaxParts = DN_MT_MAX_PARTS;  // at most this many parts per jump
 
 // a ^ b ^ c in one VALU instruction (gfx950 v_bitop3_b32, truth table 0x96;
 // hipcc keeps two v_xor_b32 otherwise).  Inline asm on purpose in the jump
@@ -273,36 +197,24 @@ __device__ __forceinline__ void jump_mega(uint32_t (&Q)[11], const Lanes& L, con
   }
 }
 
-// DN_MT_JUMP_SMEM (default 1): a run's 11 words of g are read up front by
-// scalar loads (g is read-only for the kernel's lifetime: the constant
-// address space) — one wait per run, the chunk values extracted on the scalar
-// unit (~70 fewer VALU per step) — instead of a vector load per step whose
-// vmcnt(0) opened every step: the 2^24 level 171.6 vs 180.0 us on average,
-// make_shares_vec 2^20 -2 % (profiles/r05/y/).
-#ifndef DN_MT_JUMP_SMEM
-#define DN_MT_JUMP_SMEM 1
-#endif
+// A run's 11 words of g are read up front by scalar loads (g is read-only
+// for the kernel's lifetime: the constant address space) — one wait per run,
+// the chunk values extracted on the scalar unit (~70 fewer VALU per step) —
+// instead of a vector load per step whose vmcnt(0) opened every step: the
+// 2^24 level 171.6 vs 180.0 us on average, make_shares_vec 2^20 -2 %
+// (profiles/r05/y/).
 typedef __attribute__((address_space(4))) const uint64_t const_u64_t;
 
 template <int... ks>
 __device__ __forceinline__ void jump_run(uint32_t (&Q)[11], const Lanes& L, const uint32_t* E,
                                          const uint32_t (&off)[16], const uint64_t* g, int wi, int top,
                                          std::integer_sequence<int, ks...>) {
-#if DN_MT_JUMP_SMEM
   const_u64_t* gc = (const_u64_t*)(g);
   const int tu = __builtin_amdgcn_readfirstlane(top);
   uint64_t gws[sizeof...(ks)];
   ((void)(gws[ks] = gc[__builtin_amdgcn_readfirstlane(wi - ks <= tu ? wi - ks : tu)]), ...);  // in range
   ((void)(gws[ks] = (wi - ks) <= tu ? gws[ks] : 0ull), ...);
   ((void)jump_mega<ks>(Q, L, E, off, gws[ks]), ...);
-#else
-  ((void)[&] {
-     const int w = wi - ks;
-     const uint64_t gw = w <= top ? g[w] : 0ull;
-     jump_mega<ks>(Q, L, E, off, gw);
-   }(),
-   ...);
-#endif
 }
 
 // One workgroup = up to W jumps (or parts of jumps, words [lo, hi) of g)
@@ -352,7 +264,6 @@ __global__ void __launch_bounds__(64 * W) mt_jump_kernel(const JumpArgs a) {
     for (uint32_t i = tid; i < 687u; i += 64u * W) ext[i] = ring[(64u * static_cast<uint32_t>(lo) + i) & 1023u];
     __syncthreads();
   }
-#if DN_JUMP_TABLE_POS
   // One thread per stream position q = 64 k + m (row k = 0..10 of the frame,
   // m = 0..63; T-stream word j = q - 16, zero outside 0..683): the 16
   // combinations of words j..j+3 from four LDS reads, stored to the main half
@@ -379,21 +290,6 @@ __global__ void __launch_bounds__(64 * W) mt_jump_kernel(const JumpArgs a) {
       if (ew) ew[v * kEVWords] = c[v];
     }
   }
-#else
-  for (uint32_t e = tid; e < static_cast<uint32_t>(kEWords); e += 64u * W) {
-    const uint32_t wrap = e >= static_cast<uint32_t>(kEWrap) ? 1u : 0u, re = e - wrap * kEWrap;
-    const uint32_t i = re / kEPair, rem = re - i * kEPair;  // pair plane, position in it
-    const uint32_t v = rem / kEVWords, mw = rem - v * kEVWords, m = mw >> 1;
-    // T-stream word; -1 in the gap before the wrap half and the 2 pad words of a plane
-    const int j = (i < 5u && v < 16u) ? 64 * static_cast<int>(2 * i + (mw & 1u) + wrap) + static_cast<int>(m) - 16 : -1;
-    uint32_t x = 0u;
-    if (j >= 0 && j < 684) {
-#pragma unroll
-      for (int b = 0; b < 4; ++b) x ^= ext[j + b] & (0u - ((v >> b) & 1u));
-    }
-    E[e] = x;
-  }
-#endif
   __syncthreads();
   if (j0 + wid >= a.njobs || dsti < 0) return;
 
@@ -613,17 +509,9 @@ __global__ void __launch_bounds__(64 * W, CB == 4 ? 8 : 1) mt_jumpc_kernel(const
   }
 }
 
-// The chunk width of the kernel beside the generation (DN_MT_BESIDE_CB, 2 or
-// 3; tuning build: the env variable of that name)
-#ifndef DN_MT_BESIDE_CB
-#define DN_MT_BESIDE_CB 2
-#endif
-int beside_cb() {
-  const char* e = tune_env("DN_MT_BESIDE_CB");
-  return e ? (e[0] == '2' ? 2 : 3) : DN_MT_BESIDE_CB;
-}
-void launch_jumpc4(dim3 grid, hipStream_t s, const JumpArgs& ja) {
-  if (beside_cb() == 2) hipLaunchKernelGGL((mt_jumpc_kernel<4, 2>), grid, dim3(256), 0, s, ja);
+// cb: the chunk width of the kernel beside the generation, 2 or 3 (MtKnobs::beside_cb)
+void launch_jumpc4(dim3 grid, hipStream_t s, const JumpArgs& ja, int cb) {
+  if (cb == 2) hipLaunchKernelGGL((mt_jumpc_kernel<4, 2>), grid, dim3(256), 0, s, ja);
   else hipLaunchKernelGGL((mt_jumpc_kernel<4, 3>), grid, dim3(256), 0, s, ja);
 }
 
@@ -692,20 +580,6 @@ struct GenArgs {
 #else
 #define DN_PROBE_SKIP(a, bit)
 #endif
-
-// Substream s runs forward from W(s) unless backward generation is on
-// (back = 1) and s is even, not 0 and not the last (then backward from
-// W(s + 1)).  back = 2 (tuning build, DN_MT_BACK=2: a probe of the backward
-// generation rate) runs every substream but the first and the last backward.
-__host__ __device__ inline bool mt_sub_forward(uint32_t s, uint64_t S, int back) {
-  if (back == 2) return s == 0u || s + 1u >= S;
-  return !back || s == 0u || (s & 1u) || s + 1u >= S;
-}
-
-// W(s) is jumped to when substream s starts from it or substream s - 1 ends on it.
-__host__ __device__ inline bool mt_window_needed(uint32_t s, uint64_t S, int back) {
-  return mt_sub_forward(s, S, back) || !mt_sub_forward(s - 1u, S, back);
-}
 
 // Raw (untempered) words of a substream pass through an LDS ring of M words
 // (M = two emission groups): stream word p sits at slot (p + delta) mod M,
@@ -1530,287 +1404,6 @@ __global__ void __launch_bounds__(128, T == 5 ? 2 : 4) mt_gen_pc_kernel(const Ge
   }
 }
 
-uint64_t mt_subs(uint64_t ncoef) {
-  const uint64_t d = mt_sub_draws(mt_sub_len(ncoef));
-  return (ncoef + d - 1) / d;
-}
-
-constexpr int32_t kFullSpan = kMtPolyWords << 16;  // words [0, 312)
-constexpr uint64_t kPartRows = 4096;  // part windows of one split level (jumps x parts <= 4096)
-
-// The jobs of one level: W waves per workgroup (one job each; padding jobs
-// have dst -1), grouped by source window and part (one table per workgroup).
-struct Level {
-  int W = 8;
-  std::vector<JumpJob> jobs;
-  std::vector<CombineJob> comb;
-};
-
-void push_group(Level& L, int32_t src, const std::vector<std::pair<int32_t, int32_t>>& pd, int32_t span) {
-  for (size_t i = 0; i < pd.size(); ++i) L.jobs.push_back({src, pd[i].first, pd[i].second, span});
-  while (L.jobs.size() % static_cast<size_t>(L.W)) L.jobs.push_back({src, 0, -1, span});
-}
-
-// a source's jobs in groups of at most `per`
-void push_groups(Level& L, int32_t src, const std::vector<std::pair<int32_t, int32_t>>& pd, size_t per,
-                 int32_t span = kFullSpan) {
-  for (size_t i = 0; i < pd.size(); i += per)
-    push_group(L, src, std::vector<std::pair<int32_t, int32_t>>(pd.begin() + i, pd.begin() + std::min(pd.size(), i + per)),
-               span);
-}
-
-// One level: (source, [(poly, dst)]) lists of n jumps in all.  A jump's
-// Horner chain is ~312 dependent steps of LDS-table reads, so the level is
-// latency-bound unless every CU holds many waves.  The level therefore splits
-// each jump into P = min(16, 4096 / n) parts over word ranges of g (n P part
-// jobs, each ~312 / P steps, written to part rows prow0 .. and XORed into the
-// jump's window by mt_combine_kernel) and groups per = clamp(n P / 256, 2,
-// 16) part jobs of one source and part per workgroup (one table): ~256
-// workgroups, one per CU (82 KB of LDS each), 2..16 waves.  Large levels
-// (n >= 4096) stay whole, 16 jumps per workgroup.
-// Word ranges [cut[j], cut[j + 1]) of g for at most P parts.  A part costs
-// its Horner steps — whole runs of 11 words (jump_run), the words above g's
-// top included — plus the stepping of its source stream to word 64 lo, about
-// r runs' worth per word of lo (r ~ 0.053 / 11 for 8-wave workgroups, ~0.014 / 11
-// for 16-wave ones: profiles/r03/ab/jump_probe/).  Parts nearer the top of g
-// start further down the stream, so they get fewer runs: the smallest cost
-// bound T (in steps) the greedy split meets with at most P parts.
-std::vector<int32_t> part_cuts(int P, int W) {
-  const double r = W >= 16 ? 0.014 : 0.053;  // stepping cost per word of lo, in Horner steps
-  const int runs_total = (kMtPolyWords + 10) / 11;
-  for (int T = 11; ; T += 1) {
-    std::vector<int32_t> cut{0};
-    while (cut.back() < kMtPolyWords && static_cast<int>(cut.size()) <= P) {
-      const int lo = cut.back();
-      const int runs = static_cast<int>((T - r * lo) / 11.0);
-      if (runs < 1) break;
-      cut.push_back(std::min(kMtPolyWords, lo + 11 * runs));
-    }
-    if (cut.back() >= kMtPolyWords && static_cast<int>(cut.size()) - 1 <= P) return cut;
-    if (T > 11 * runs_total + 1000) break;
-  }
-  std::vector<int32_t> cut;  // unreachable: one part of all the words
-  for (int j = 0; j <= P; ++j) cut.push_back(kMtPolyWords * j / P);
-  return cut;
-}
-
-void push_level(Level& L, const std::vector<std::pair<int32_t, std::vector<std::pair<int32_t, int32_t>>>>& srcs,
-                int32_t prow0, int p_force = 0, int w_force = 0) {
-  size_t n = 0, most = 0;  // jumps, and the most of one source
-  for (auto& sp : srcs) n += sp.second.size(), most = std::max(most, sp.second.size());
-  if (n == 0) return;
-  int P = static_cast<int>(std::max<size_t>(1, std::min<size_t>(kMaxParts, kPartRows / n)));
-  if (p_force > 0) P = std::min(p_force, kMaxParts);
-  // DN_MT_PARTS_B (tuning build): the part count of levels of 256 jumps or more
-  const char* pb = n >= 256 ? tune_env("DN_MT_PARTS_B") : nullptr;
-  if (pb && std::atoi(pb) >= 1) P = std::min(kMaxParts, std::atoi(pb));
-  size_t per = std::min<size_t>(kJumpWaves, std::max<size_t>(2, (n * P + 255) / 256));
-  L.W = std::min(per, most) > 8 ? 16 : 8;
-  if (w_force > 0) L.W = w_force, per = static_cast<size_t>(w_force);  // (mt_jumpc_kernel's workgroups)
-  if (P == 1) {
-    for (auto& sp : srcs) push_groups(L, sp.first, sp.second, per);
-    return;
-  }
-  const std::vector<int32_t> cut = part_cuts(P, L.W);
-  P = static_cast<int>(cut.size()) - 1;
-  int32_t row = prow0;
-  for (auto& sp : srcs)
-    for (auto& pd : sp.second) {
-      L.comb.push_back({pd.second, row, P, 0});
-      row += P;
-    }
-  for (int j = 0; j < P; ++j) {
-    const int32_t lo = cut[j], hi = cut[j + 1];
-    row = prow0 + j;
-    for (auto& sp : srcs) {
-      std::vector<std::pair<int32_t, int32_t>> pd;
-      for (auto& q : sp.second) {
-        pd.push_back({q.first, row});
-        row += P;
-      }
-      push_groups(L, sp.first, pd, per, lo | hi << 16);
-    }
-  }
-}
-
-// Levels for windows 1 .. S-1 (s - 1 = 4096 c + 64 a + b; row S holds W_idx;
-// part rows from S + 1) with the jump table of substream length ki:
-// A: W(1 + 64 a) = A_a(W_idx); C: W(1 + 4096 c + 64 a) = C_c(W(1 + 64 a));
-// B: W(base + b) = B_b(W(base)).  back: only the windows a generation wave
-// starts from (mt_sub_forward: odd s, the last one) — A and C windows are odd.
-// rt: one direct level through the runtime rows (host_gf2poly.cpp) for the
-// draws of up to kMtRtRows + 1 substreams of 2^14 draws that generate
-// backward: the 1024 windows of a 2^24-element 3-of-5 draw in one level of
-// ~150 us instead of level A (~28 us), its combine and level B (~148 us).
-// The first substream of split2's second half: even, so the first half's
-// last substream (odd) runs forward from a window of the first half, and every
-// even substream runs backward from a window of its own half.
-inline uint64_t mt_split_half(uint64_t S) { return (S / 2 + 1) & ~1ull; }
-
-// split2 (DN_MT_SPLIT2): the runtime direct level as two levels, the windows
-// of substreams [0, S/2) and of [S/2, S), at the whole level's part count, so
-// the first half's generation can start while the second half's jumps run.
-void build_levels(uint64_t S, int ki, int back, bool rt, Level lv[3], bool split2 = false) {
-  const uint64_t R = kMtJumpRadix;
-  if (S < 2) return;
-  const uint64_t last = S - 2;  // largest s - 1
-  const int32_t prow0 = static_cast<int32_t>(S + 1);
-  if (rt && split2) {
-    const uint64_t half = mt_split_half(S);
-    std::vector<std::pair<int32_t, int32_t>> pd1, pd2;
-    for (uint64_t s = 1; s < S; ++s)
-      if (mt_window_needed(static_cast<uint32_t>(s), S, back))
-        (s < half ? pd1 : pd2).push_back({kMtRtBase + static_cast<int32_t>(s - 1), static_cast<int32_t>(s)});
-    const int P = static_cast<int>(std::max<size_t>(1, std::min<size_t>(kMaxParts, kPartRows / (pd1.size() + pd2.size()))));
-    push_level(lv[0], {{-1, pd1}}, prow0, P);
-    int32_t prow1 = prow0;
-    for (auto& c : lv[0].comb) prow1 = std::max(prow1, c.first + c.parts);
-    push_level(lv[1], {{-1, pd2}}, prow1, P);
-    return;
-  }
-  if (rt) {
-    std::vector<std::pair<int32_t, int32_t>> pd;
-    for (uint64_t s = 1; s < S; ++s)
-      if (mt_window_needed(static_cast<uint32_t>(s), S, back))
-        pd.push_back({kMtRtBase + static_cast<int32_t>(s - 1), static_cast<int32_t>(s)});
-    push_level(lv[0], {{-1, pd}}, prow0);
-    return;
-  }
-  if (last < static_cast<uint64_t>(kMtDirectRows)) {
-    // every window one jump from W_idx: W(s) = D_s(W_idx), one level
-    std::vector<std::pair<int32_t, int32_t>> pd;
-    for (uint64_t s = 1; s < S; ++s)
-      if (mt_window_needed(static_cast<uint32_t>(s), S, back))
-        pd.push_back({kMtDirectBase + ki * kMtDirectRows + static_cast<int32_t>(s - 1), static_cast<int32_t>(s)});
-    push_level(lv[0], {{-1, pd}}, prow0);
-    return;
-  }
-  const int32_t t0 = ki * kMtJumpRows;  // the table's first row
-  {
-    std::vector<std::pair<int32_t, int32_t>> pd;
-    for (uint64_t a = 0; a <= last / R && a < R; ++a)
-      pd.push_back({t0 + kMtRowA + static_cast<int32_t>(a), static_cast<int32_t>(1 + R * a)});
-    push_level(lv[0], {{-1, pd}}, prow0);  // source: W_idx, the row before row 0
-  }
-  {
-    std::vector<std::pair<int32_t, std::vector<std::pair<int32_t, int32_t>>>> srcs;
-    for (uint64_t a = 0; a < R && R * a <= last; ++a) {  // C: per source W(1 + 64 a), its c digits
-      std::vector<std::pair<int32_t, int32_t>> pd;
-      for (uint64_t c = 1; c < R && R * R * c + R * a <= last; ++c)
-        pd.push_back({t0 + kMtRowC + static_cast<int32_t>(c), static_cast<int32_t>(1 + R * R * c + R * a)});
-      if (!pd.empty()) srcs.push_back({static_cast<int32_t>(1 + R * a), pd});
-    }
-    push_level(lv[1], srcs, prow0);
-  }
-  {
-    std::vector<std::pair<int32_t, std::vector<std::pair<int32_t, int32_t>>>> srcs;
-    for (uint64_t base = 0; base <= last; base += R) {  // B: per source W(1 + base)
-      std::vector<std::pair<int32_t, int32_t>> pd;
-      for (uint64_t b = 1; b < R && base + b <= last; ++b)
-        if (mt_window_needed(static_cast<uint32_t>(1 + base + b), S, back))
-          pd.push_back({t0 + kMtRowB + static_cast<int32_t>(b), static_cast<int32_t>(1 + base + b)});
-      if (!pd.empty()) srcs.push_back({static_cast<int32_t>(1 + base), pd});
-    }
-    push_level(lv[2], srcs, prow0);
-  }
-}
-
-// Per-thread host side of a draw: the job tables of the last substream count
-// and length (they depend on S and ki only; plain host memory, freed with the
-// thread).
-struct MtHost {
-  uint64_t S = ~0ull;
-  int ki = -1;
-  int back = 0;
-  int parts_b = 0;  // tuning build: DN_MT_PARTS_B the levels were built with
-  bool rt = false;  // one direct level through the runtime rows
-  bool split2 = false;  // that level in two halves (DN_MT_SPLIT2)
-  Level lv[3];
-  Level beside;  // rt: the direct level for mt_jumpc_kernel<4, 2> (whole jumps, 4 per workgroup)
-  Level j0;      // rt: one jump, row S -> row -1 by x^(17 ncoef) (the rt pointer), in parts, mt_jumpc_kernel<4, 2>
-  std::vector<uint32_t> jobs;  // the levels' jobs, their combine jobs, beside's jobs, j0's jobs and combine job
-  uint64_t beside_off = 0, j0_off = 0, j0_comb_off = 0;  // word offsets in `jobs`
-  uint64_t part_rows = 0;      // part windows the largest split level writes (levels reuse them)
-};
-thread_local MtHost tls_mt;
-
-// Backward generation of the even substreams (on; DN_MT_BACK=0 in the tuning
-// build turns it off for A/B).
-int mt_back() {
-  const char* e = tune_env("DN_MT_BACK");
-  return e ? (e[0] == '0' ? 0 : e[0] == '2' ? 2 : 1) : 1;
-}
-
-MtHost& mt_levels(uint64_t S, int ki) {
-  MtHost& H = tls_mt;
-  // 2^8-draw substreams run forward only: at t = 5 one holds a single
-  // emission group, and backward generation needs an even count (its window
-  // is the top of ring half 1); their one direct level takes the extra jumps
-  const int back = ki == 3 ? 0 : mt_back();
-  const char* pb = tune_env("DN_MT_PARTS_B");
-  const int parts_b = pb ? std::atoi(pb) : 0;
-  // the runtime direct level: 2^14-draw substreams generating backward, more
-  // than the tabulated direct rows cover, at most kMtRtRows + 1 of them, and
-  // rows available on this host (DN_MT_RT=0, tuning build: off)
-  const char* rte = tune_env("DN_MT_RT");
-  const bool rt = DN_MT_RT_DIRECT && !(rte && rte[0] == '0') && ki == 2 && back == 1 &&
-                  S - 1 > static_cast<uint64_t>(kMtDirectRows) && S - 1 <= kMtRtRows &&
-                  mt_direct_rows_l14(S, nullptr) != nullptr;
-  const char* sp = tune_env("DN_MT_SPLIT2");
-  const bool split2 = rt && (sp ? sp[0] == '1' : DN_MT_SPLIT2 != 0) && S >= 4;
-  if (H.S != S || H.ki != ki || H.back != back || H.parts_b != parts_b || H.rt != rt || H.split2 != split2) {
-    for (auto& l : H.lv) l = Level();
-    build_levels(S, ki, back, rt, H.lv, split2);
-    H.beside = Level();
-    H.j0 = Level();
-    if (rt && !split2) {
-      std::vector<std::pair<int32_t, int32_t>> pd;
-      for (uint64_t s = 1; s < S; ++s)
-        if (mt_window_needed(static_cast<uint32_t>(s), S, back))
-          pd.push_back({kMtRtBase + static_cast<int32_t>(s - 1), static_cast<int32_t>(s)});
-      push_level(H.beside, {{-1, pd}}, static_cast<int32_t>(S + 1), 1, 4);
-    }
-    // the next call's W_idx for a speculation beside the generation (any
-    // shape with jump levels: the levels of a small generation run beside it
-    // as they are, mt_device_run)
-    if (!split2 && S >= 2)
-      push_level(H.j0, {{static_cast<int32_t>(S), {{kMtRtBase, -1}}}}, static_cast<int32_t>(S + 1), kMaxParts, 4);
-    uint64_t nj = 0, nc = 0;
-    for (auto& l : H.lv) nj += l.jobs.size(), nc += l.comb.size();
-    nj += H.beside.jobs.size() + H.j0.jobs.size();
-    nc += H.j0.comb.size();
-    H.part_rows = 0;
-    for (auto& l : H.lv)
-      for (auto& c : l.comb) H.part_rows = std::max<uint64_t>(H.part_rows, c.first + c.parts - (S + 1));
-    for (auto& c : H.j0.comb) H.part_rows = std::max<uint64_t>(H.part_rows, c.first + c.parts - (S + 1));
-    H.jobs.assign((nj * sizeof(JumpJob) + nc * sizeof(CombineJob)) / 4, 0u);
-    uint64_t o = 0;
-    for (auto& l : H.lv) {
-      std::memcpy(H.jobs.data() + o, l.jobs.data(), l.jobs.size() * sizeof(JumpJob));
-      o += l.jobs.size() * sizeof(JumpJob) / 4;
-    }
-    for (auto& l : H.lv) {
-      std::memcpy(H.jobs.data() + o, l.comb.data(), l.comb.size() * sizeof(CombineJob));
-      o += l.comb.size() * sizeof(CombineJob) / 4;
-    }
-    H.beside_off = o;
-    std::memcpy(H.jobs.data() + o, H.beside.jobs.data(), H.beside.jobs.size() * sizeof(JumpJob));
-    o += H.beside.jobs.size() * sizeof(JumpJob) / 4;
-    H.j0_off = o;
-    std::memcpy(H.jobs.data() + o, H.j0.jobs.data(), H.j0.jobs.size() * sizeof(JumpJob));
-    o += H.j0.jobs.size() * sizeof(JumpJob) / 4;
-    H.j0_comb_off = o;
-    std::memcpy(H.jobs.data() + o, H.j0.comb.data(), H.j0.comb.size() * sizeof(CombineJob));
-    H.S = S;
-    H.ki = ki;
-    H.back = back;
-    H.parts_b = parts_b;
-    H.rt = rt;
-    H.split2 = split2;
-  }
-  return H;
-}
-
 // Pinned staging buffers for a draw's small copies (from pageable memory HIP
 // stages every copy through a buffer of its own and the host waits for it).
 // A process-wide pool: a call leases one for its duration — every call
@@ -1858,17 +1451,6 @@ struct PinLease {
   PinLease(const PinLease&) = delete;
   PinLease& operator=(const PinLease&) = delete;
 };
-
-constexpr uint64_t kHead = 2816;  // flag (4 B at 0), final array (2496 B at 256), pad to 256 B
-
-// DN_MT_HOST_HEAD = 1: the generation writes the flag and CPython's final
-// array straight into the call's pinned staging buffer (mapped host memory,
-// visible once the stream has synchronised) instead of the scratch head and
-// a device-to-host copy after it.
-// (make_shares_vec 2^12 -1.5 us: no read-back copy; profiles/r04/e/)
-#ifndef DN_MT_HOST_HEAD
-#define DN_MT_HOST_HEAD 1
-#endif
 
 // The levels' job tables on the device, one upload per (device, shape): they
 // depend on (S, ki, back, parts) only, so a call copies just its own state
@@ -1954,25 +1536,12 @@ const uint64_t* device_rt(uint64_t S, int* err) {
   return d->p;
 }
 
-// The call's end: DN_MT_SPIN_SYNC = 1 records an event behind the last
-// launch and polls it (the thread spins instead of blocking in the runtime:
-// a shorter wake-up for a call whose GPU work is tens of microseconds);
-// otherwise hipStreamSynchronize.  One event per thread, created once.
-#ifndef DN_MT_SPIN_SYNC
-#define DN_MT_SPIN_SYNC 0
-#endif
-// DN_MT_SPLIT2's side stream and its two events, per thread and device
-// (created once, never destroyed: the runtime may be torn down first).
+// split2's side stream and its two events, per thread and device (created
+// once, never destroyed: the runtime may be torn down first).
 struct SideStream {
   int dev = -1;
   hipStream_t s = nullptr;
   hipEvent_t levels = nullptr, gen = nullptr;
-  // DN_MT_SPEC_PROBE: the prefix copied, the side levels done (pending: a
-  // wait owed by the next call), the side levels' own buffer
-  hipEvent_t copy = nullptr, spec = nullptr;
-  bool pending = false;
-  void* buf = nullptr;
-  uint64_t buf_bytes = 0;
 };
 SideStream* side_stream() {
   thread_local SideStream side[16];
@@ -1982,16 +1551,74 @@ SideStream* side_stream() {
   if (!x.s) {
     if (hipStreamCreateWithFlags(&x.s, hipStreamNonBlocking) != hipSuccess) return x.s = nullptr, nullptr;
     if (hipEventCreateWithFlags(&x.levels, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.gen, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.copy, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&x.spec, hipEventDisableTiming) != hipSuccess)
+        hipEventCreateWithFlags(&x.gen, hipEventDisableTiming) != hipSuccess)
       return nullptr;
     x.dev = dev;
   }
   return &x;
 }
 
-// DN_MT_SPEC (default 1; tuning build: DN_MT_SPEC=0 off): a call speculates
+// Every knob of a run, with the product's values as the defaults: the
+// product build reads no environment variable (tune_env), the tuning build
+// reads each DN_MT_* variable of that name once per call, here.  (The
+// planner's own knobs — DN_MT_BACK, _RT, _SPLIT2, _PARTS_B — are mt_plan.hpp's.)
+struct MtKnobs {
+  // a call speculates on its successor (SpecState, below; DN_MT_SPEC=0 off)
+  bool spec = true;
+  // The final state by the last substream (last_sub_tail) rather than a
+  // final-state wave (DN_MT_TAIL_FIN=0): that wave stepped the whole last
+  // substream again, one wave alone, and finished ~100 us after the other
+  // substreams at 2^24 (profiles/r06/g/timeline_spec.json: substreams
+  // 0.88-0.91 ms, the wave 0.93-1.09 ms).
+  bool tail_fin = true;
+  // the speculated levels of a runtime-direct-level draw (2^24 scale) beside
+  // the generation rather than after it (DN_MT_SPEC_BESIDE=0 off), by
+  // mt_jumpc_kernel<4, beside_cb> (DN_MT_BESIDE_CB, 2 or 3)
+  bool spec_beside = true;
+  int beside_cb = 2;
+  // draws of fewer coefficients than spec_min do not speculate after the
+  // generation (DN_MT_SPEC_MIN), nor beside it below beside_min
+  // (DN_MT_BESIDE_MIN: the levels of a small generation beside it, round 6)
+  uint64_t spec_min = 1ull << 23, beside_min = 1ull << 16;
+  // DN_MT_SPEC_PROBE=5: the call's own runtime direct level by
+  // mt_jumpc_kernel<4, beside_cb> (its time alone, and the kernel's test); no
+  // speculation.  (Values 1-4 were timing probes with wrong output, retired.)
+  bool own_by_jumpc = false;
+  uint32_t jump_probe = 0;  // DN_MT_JUMP_PROBE (JumpArgs::probe)
+  bool jump4b = false;      // DN_MT_JUMP4B=1: 16-wave levels by mt_jumpc_kernel<16, 4>
+  uint32_t gen_probe = 0;   // DN_MT_PROBE (GenArgs::probe)
+  bool pc = true;           // DN_MT_PC_FORCE=0: the one-wave generation kernel (A/B)
+  // DN_MT_GEN_SUBS (timing probe only: the output is partial and CPython's
+  // final state is not computed): launch only the first K substream
+  // workgroups — how the generation's time scales with the substreams in flight
+  uint32_t gen_subs = 0;
+  // DN_MT_FORCE_RETRY=1 takes the rejected-draw exit so the caller's host
+  // fallback can be exercised
+  bool force_retry = false;
+};
+
+MtKnobs mt_knobs() {
+  MtKnobs k;
+  auto on = [](const char* n, bool dflt) { const char* e = tune_env(n); return e ? e[0] != '0' : dflt; };
+  auto is1 = [](const char* n) { const char* e = tune_env(n); return e && e[0] == '1'; };
+  auto num = [](const char* n) { const char* e = tune_env(n); return e ? std::atoi(e) : 0; };
+  k.spec = on("DN_MT_SPEC", k.spec);
+  k.tail_fin = on("DN_MT_TAIL_FIN", k.tail_fin);
+  k.spec_beside = on("DN_MT_SPEC_BESIDE", k.spec_beside);
+  if (const char* e = tune_env("DN_MT_BESIDE_CB")) k.beside_cb = e[0] == '2' ? 2 : 3;
+  if (const char* e = tune_env("DN_MT_SPEC_MIN")) k.spec_min = std::strtoull(e, nullptr, 10);
+  if (const char* e = tune_env("DN_MT_BESIDE_MIN")) k.beside_min = std::strtoull(e, nullptr, 10);
+  k.own_by_jumpc = num("DN_MT_SPEC_PROBE") == 5;
+  k.jump_probe = static_cast<uint32_t>(num("DN_MT_JUMP_PROBE"));
+  k.jump4b = is1("DN_MT_JUMP4B");
+  k.gen_probe = static_cast<uint32_t>(num("DN_MT_PROBE"));
+  k.pc = on("DN_MT_PC_FORCE", k.pc);
+  if (tune_env("DN_MT_GEN_SUBS")) k.gen_subs = static_cast<uint32_t>(std::max(1, num("DN_MT_GEN_SUBS")));
+  k.force_retry = is1("DN_MT_FORCE_RETRY");
+  return k;
+}
+
+// Speculation (MtKnobs::spec): a call speculates
 // that the next draw on this device has the same size and starts where this
 // one ends — the loop `for x in batch: make_shares_vec(x)` — and computes the
 // next call's windows while its own host side finishes: the generation's last
@@ -2008,32 +1635,6 @@ SideStream* side_stream() {
 // stream fills); the side stream's work is always awaited by the call stream
 // before a buffer is reused.  One state per device, process-wide; a call that
 // finds it busy (another thread's call) neither speculates nor hits.
-#ifndef DN_MT_SPEC
-#define DN_MT_SPEC 1
-#endif
-// The final state by the last substream (tail_fin, last_sub_tail) rather than
-// a final-state wave: that wave stepped the whole last substream again, one
-// wave alone, and finished ~100 us after the other substreams at 2^24
-// (profiles/r06/g/timeline_spec.json: substreams 0.88-0.91 ms, the wave
-// 0.93-1.09 ms).
-#ifndef DN_MT_TAIL_FIN
-#define DN_MT_TAIL_FIN 1
-#endif
-// The speculated levels of a runtime-direct-level draw (2^24 scale) beside
-// the generation rather than after it (mt_jumpc_kernel<4, 2>; tuning build:
-// DN_MT_SPEC_BESIDE=0 off)
-#ifndef DN_MT_SPEC_BESIDE
-#define DN_MT_SPEC_BESIDE 1
-#endif
-// draws of fewer coefficients than this do not speculate after the
-// generation (tuning build: DN_MT_SPEC_MIN), nor beside it below
-// DN_MT_BESIDE_MIN (the levels of a small generation beside it, round 6)
-#ifndef DN_MT_SPEC_MIN
-#define DN_MT_SPEC_MIN (1ull << 23)
-#endif
-#ifndef DN_MT_BESIDE_MIN
-#define DN_MT_BESIDE_MIN (1ull << 16)
-#endif
 struct SpecState {
   std::mutex m;
   hipStream_t side = nullptr, side2 = nullptr;
@@ -2117,44 +1718,255 @@ bool spec_buffers(SpecState& sp, uint64_t need) {
   return true;
 }
 
-hipError_t mt_wait(hipStream_t s) {
-#if DN_MT_SPIN_SYNC
-  thread_local hipEvent_t ev = nullptr;
-  if (!ev && hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) {
-    ev = nullptr;
-    return hipStreamSynchronize(s);
-  }
-  hipError_t e = hipEventRecord(ev, s);
-  if (e != hipSuccess) return e;
-  while ((e = hipEventQuery(ev)) == hipErrorNotReady) {
-  }
-  return e;
-#else
-  return hipStreamSynchronize(s);
-#endif
-}
-
-}  // namespace
-}  // namespace dn
-
-using namespace dn;
-
-extern "C" uint64_t dn_mt19937_device_scratch_bytes(uint64_t n_elem, int tm1) {
-  const uint64_t ncoef = tm1 > 0 ? n_elem * static_cast<uint64_t>(tm1) : 0;
-  const uint64_t S = ncoef ? mt_subs(ncoef) : 0;
-  if (!S) return kHead + kMtN * 4;
-  const MtHost& H = mt_levels(S, mt_sub_len(ncoef));
-  return kHead + (1 + S + 1 + H.part_rows) * kMtN * 4;
-}
-
-namespace dn {
-namespace {
-
-// The device draw of n_elem * tm1 coefficients from CPython state
-// (mt_state, *mt_index): jump levels, then `launch_gen(ga, S)` (the
-// generation kernel: coefficients or fused split), then CPython's final state.
 constexpr uint64_t kCus = 256, kLdsPerCu = 160 * 1024;  // MI355X: CUs, LDS bytes per CU
 
+// What a call decides about speculation: whether its own windows were
+// speculated by the previous call, and whether and how it speculates on the
+// next one.
+struct SpecPlan {
+  bool hit = false;        // this call's windows are in place, in sp->buf[sp->next]
+  bool spec_next = false;  // the next call's windows go to sp->buf[dst] ...
+  bool beside = false;     // ... beside this call's generation rather than after it
+  bool widx2 = false;      // beside: the previous call left the next call's W_idx in place
+  int dst = 0;
+};
+
+// sp: the device's speculation state, held by this call (null: none).
+// beside (runtime direct level): the next call's W_idx by one jump from this
+// call's, then its level, both by mt_jumpc_kernel<4, 2> on the side stream
+// beside this call's generation.  Other shapes: the levels as they are
+// (mt_jump_kernel, 83 KB workgroups) when the generation's rings leave a CU
+// that much LDS (a generation of at most ~1000 3-of-5 substreams: 2^22
+// coefficients and less), and when the generation outlasts them: substreams
+// of 2^12 draws, or of 2^10 and at most 256 of them (loops of 2^20 / 2^16
+// elements -15 / -10 %; 512 substreams of 2^10 draws, 2^18 elements, +2.5 %:
+// profiles/r06/y/).
+SpecPlan spec_decide(SpecState* sp, const MtKnobs& k, const MtHost& H, uint64_t ncoef, int ring_units, int32_t idx,
+                     const uint32_t* mt_state) {
+  SpecPlan p;
+  if (!sp) return p;
+  // this call continues the previous one (same size, starting where it
+  // ended): a hit if that call speculated, and a reason to speculate again
+  const bool cont = sp->have_end && sp->ncoef == ncoef && sp->idx == idx && !std::memcmp(sp->state, mt_state, kMtN * 4);
+  p.hit = cont && sp->armed;
+  if (sp->armed && !p.hit) ++sp->misses;
+  p.widx2 = p.hit && sp->widx2;
+  sp->armed = false;
+  sp->widx2 = false;
+  sp->have_end = false;
+  p.spec_next = cont && spec_buffers(*sp, mt_scratch_bytes(ncoef));
+  const uint64_t gen_lds = (1u + 2u * 17u * 64u * static_cast<uint32_t>(ring_units) + 64u) * 4u;
+  const bool levels_fit = (H.S + kCus - 1) / kCus * gen_lds + (kEWords + kMtN + 64) * 4u <= kLdsPerCu;
+  p.beside = p.spec_next && k.spec_beside && ncoef >= k.beside_min &&
+             (H.rt ? !H.beside.jobs.empty() : levels_fit && (mt_sub_draws(H.ki) >= 4096 || H.S <= 256)) &&
+             !H.j0.jobs.empty() && spec_xpow(*sp, 17 * ncoef);
+  if (!p.beside && ncoef < k.spec_min) p.spec_next = false;  // (no speculation after the generation this small)
+  p.dst = sp->next ^ 1;
+  return p;
+}
+
+// Where the call ended; the next call, if it starts here, uses the
+// speculated windows (spec_next) or speculates itself.
+void spec_record_end(SpecState& sp, const SpecPlan& p, uint64_t ncoef, int32_t fidx, const uint32_t* mt_state) {
+  sp.have_end = true;
+  sp.ncoef = ncoef;
+  sp.idx = fidx;
+  std::memcpy(sp.state, mt_state, kMtN * 4);
+  sp.armed = p.spec_next;
+  sp.widx2 = p.beside;  // this call's buffer now holds the W_idx after the next call's
+  if (p.spec_next) sp.next = p.dst;
+}
+
+// What the launches of one call share.
+struct MtCall {
+  const MtKnobs& k;
+  const MtHost& H;  // the shape's levels (H.S substreams of length H.ki)
+  hipStream_t s;    // the caller's stream
+  // the buffer the generation reads its windows from (the caller's scratch or
+  // a speculation buffer): head | W_idx (row -1) | rows 0..S | part rows
+  uint8_t* sc;
+  uint32_t* dwin;          // its row 0
+  const void* jobs_dev;    // the shape's job tables on the device (MtHost::jobs)
+  const uint64_t* rt_dev;  // the runtime direct rows on the device (H.rt)
+  SpecState* sp;           // held by this call, or null
+  SideStream* side;        // split2
+};
+
+// The shape's jump levels into the windows `wins` (row 0) on stream ls;
+// after0: recorded once level 0 is complete.
+hipError_t launch_levels(const MtCall& c, hipStream_t ls, uint32_t* wins, hipEvent_t after0 = nullptr) {
+  const Level* lv = c.H.lv;
+  const JumpJob* djobs = static_cast<const JumpJob*>(c.jobs_dev);
+  const CombineJob* dcomb =
+      reinterpret_cast<const CombineJob*>(djobs + lv[0].jobs.size() + lv[1].jobs.size() + lv[2].jobs.size());
+  hipError_t err = hipSuccess;
+  uint64_t off = 0, coff = 0;
+  for (int k = 0; k < 3; ++k) {
+    const Level& l = lv[k];
+    if (!l.jobs.empty()) {
+      const JumpArgs ja{wins, djobs + off, static_cast<uint32_t>(l.jobs.size()), c.k.jump_probe, c.rt_dev};
+      const dim3 grid(static_cast<uint32_t>(l.jobs.size() / static_cast<size_t>(l.W)));
+      if (l.W == 16 && c.k.jump4b) hipLaunchKernelGGL((mt_jumpc_kernel<16, 4>), grid, dim3(64 * 16), 0, ls, ja);
+      else if (l.W == 16) hipLaunchKernelGGL(mt_jump_kernel<16>, grid, dim3(64 * 16), 0, ls, ja);
+      else hipLaunchKernelGGL(mt_jump_kernel<8>, grid, dim3(64 * 8), 0, ls, ja);
+    }
+    if (!l.comb.empty())
+      hipLaunchKernelGGL(mt_combine_kernel, dim3(static_cast<uint32_t>(l.comb.size())), dim3(640), 0, ls, wins,
+                         dcomb + coff);
+    off += l.jobs.size();
+    coff += l.comb.size();
+    if (after0 && k == 0) err = hipEventRecord(after0, ls);
+  }
+  return err;
+}
+
+// The runtime direct level by mt_jumpc_kernel<4, 2> (H.beside: whole jumps).
+void launch_beside_level(const MtCall& c, hipStream_t ls, uint32_t* wins) {
+  const Level& l = c.H.beside;
+  if (l.jobs.empty()) return;
+  const JumpJob* bj = reinterpret_cast<const JumpJob*>(static_cast<const uint32_t*>(c.jobs_dev) + c.H.beside_off);
+  const JumpArgs ja{wins, bj, static_cast<uint32_t>(l.jobs.size()), 0u, c.rt_dev};
+  launch_jumpc4(dim3(static_cast<uint32_t>(l.jobs.size() / 4)), ls, ja, c.k.beside_cb);
+}
+
+// Row S -> row -1 of the windows w by x^(17 ncoef) (H.j0: parts, then their combine).
+void jump0(const MtCall& c, hipStream_t ls, uint32_t* w) {
+  const uint32_t* hj = static_cast<const uint32_t*>(c.jobs_dev);
+  const JumpArgs j0{w, reinterpret_cast<const JumpJob*>(hj + c.H.j0_off), static_cast<uint32_t>(c.H.j0.jobs.size()), 0u,
+                    c.sp->xpow};
+  launch_jumpc4(dim3(static_cast<uint32_t>(c.H.j0.jobs.size() / 4)), ls, j0, c.k.beside_cb);
+  hipLaunchKernelGGL(mt_combine_kernel, dim3(static_cast<uint32_t>(c.H.j0.comb.size())), dim3(640), 0, ls, w,
+                     reinterpret_cast<const CombineJob*>(hj + c.H.j0_comb_off));
+}
+
+// The four ways a call launches its generation (`gen(ga, stream)`, after its
+// own levels).  err: the call's first error so far; a path goes on launching
+// after an error (the caller drains the streams) but makes no further event
+// or copy call, and returns the first error.
+struct MtLaunched {
+  hipError_t err;
+  bool side_used;  // work of this call is on the speculation side streams
+};
+
+// split2: substreams [0, S/2) on the side stream once level 0 is done (beside
+// level 1's jumps), then [S/2, S] and the final-state wave on the call's
+// stream after level 1; the call's stream then waits for the side stream.
+template <typename G>
+MtLaunched run_split2(const MtCall& c, GenArgs& ga, G gen, hipError_t err) {
+  const uint32_t half = static_cast<uint32_t>(mt_split_half(c.H.S)), nwg = ga.sub_n;
+  if (err == hipSuccess) err = hipStreamWaitEvent(c.side->s, c.side->levels, 0);
+  GenArgs g1 = ga;
+  g1.sub_lo = 0u;
+  g1.sub_n = half;
+  gen(g1, c.side->s);
+  if (err == hipSuccess) err = hipEventRecord(c.side->gen, c.side->s);
+  ga.sub_lo = half;
+  ga.sub_n = nwg - half;
+  gen(ga, c.s);
+  if (err == hipSuccess) err = hipStreamWaitEvent(c.s, c.side->gen, 0);
+  return {err, false};
+}
+
+// Speculation beside the generation.  Once this call's windows are in place,
+// in workgroups of 11 KB that fit on a CU beside the generation's rings: on
+// the side stream the next call's level into the other buffer from its W_idx
+// (row -1 there) — which the previous call computed (widx2) or, first, one
+// jump by x^(17 ncoef) from this call's W_idx computes (copied to row S, 32
+// parts + combine); on the second side stream the W_idx of the call after
+// that, jumped from the next call's into this call's buffer (rows S, part rows
+// and -1: none of them read by this call's generation).
+template <typename G>
+MtLaunched run_beside(const MtCall& c, const SpecPlan& p, GenArgs& ga, G gen) {
+  SpecState* sp = c.sp;
+  const uint64_t S = c.H.S;
+  uint8_t* nb = static_cast<uint8_t*>(sp->buf[p.dst]);
+  uint32_t* nw = reinterpret_cast<uint32_t*>(nb + kHead) + kMtN;  // the next call's row 0
+  hipError_t err = hipEventRecord(sp->win, c.s);
+  gen(ga, c.s);
+  if (err == hipSuccess) err = hipStreamWaitEvent(sp->side, sp->win, 0);
+  if (err == hipSuccess) err = hipStreamWaitEvent(sp->side2, sp->win, 0);
+  if (!p.widx2) {
+    if (err == hipSuccess)
+      err = hipMemcpyAsync(nw + S * kMtN, c.dwin - kMtN, kMtN * 4, hipMemcpyDeviceToDevice, sp->side);
+    jump0(c, sp->side, nw);
+    if (err == hipSuccess) err = hipEventRecord(sp->j0ev, sp->side);
+    if (err == hipSuccess) err = hipStreamWaitEvent(sp->side2, sp->j0ev, 0);
+  }
+  if (c.H.rt) launch_beside_level(c, sp->side, nw);
+  else (void)launch_levels(c, sp->side, nw);
+  if (err == hipSuccess) err = hipEventRecord(sp->done, sp->side);
+  if (err == hipSuccess)
+    err = hipMemcpyAsync(c.dwin + S * kMtN, nw - kMtN, kMtN * 4, hipMemcpyDeviceToDevice, sp->side2);
+  jump0(c, sp->side2, c.dwin);
+  if (err == hipSuccess) err = hipEventRecord(sp->done2, sp->side2);
+  ++sp->launched;
+  return {err, true};
+}
+
+// Speculation after the generation, whose last substream also writes the
+// next call's W_idx into row -1 of the other buffer; then on the side stream
+// the next call's jump levels from it, while this call's host side finishes
+// and the next call's begins.
+template <typename G>
+MtLaunched run_spec_after(const MtCall& c, const SpecPlan& p, GenArgs& ga, G gen) {
+  SpecState* sp = c.sp;
+  uint8_t* nb = static_cast<uint8_t*>(sp->buf[p.dst]);
+  ga.next_win = reinterpret_cast<uint32_t*>(nb + kHead);
+  gen(ga, c.s);
+  hipError_t err = hipEventRecord(sp->win, c.s);
+  if (err == hipSuccess) err = hipStreamWaitEvent(sp->side, sp->win, 0);
+  (void)launch_levels(c, sp->side, reinterpret_cast<uint32_t*>(nb + kHead) + kMtN);
+  if (err == hipSuccess) err = hipEventRecord(sp->done, sp->side);
+  ++sp->launched;
+  return {err, true};
+}
+
+template <typename G>
+MtLaunched run_plain(const MtCall& c, GenArgs& ga, G gen, hipError_t err) {
+  gen(ga, c.s);
+  return {err, false};
+}
+
+// The generation's arguments but for what the caller's launch_gen adds;
+// head: the flag (word 0) and the final array (from word 64) as the device sees them.
+GenArgs gen_args(const MtCall& c, const MtFinal& fin, bool tail_fin, int32_t idx, uint64_t n_elem, int tm1,
+                 uint32_t* head) {
+  GenArgs ga{};
+  ga.wins = c.dwin;
+  ga.flag = head;
+  ga.fin = head + 64;
+  ga.ncoef = n_elem * static_cast<uint64_t>(tm1);
+  ga.sub_draws = mt_sub_draws(c.H.ki);
+  ga.vb = dn_m521_vec_bytes(n_elem);
+  ga.tm1_magic = ((1ull << 32) + static_cast<uint64_t>(tm1) - 1) / static_cast<uint64_t>(tm1);
+  ga.S = static_cast<uint32_t>(c.H.S);
+  ga.idx = static_cast<uint32_t>(idx);
+  ga.tm1 = tm1;
+  ga.final_sig = fin.sig;
+  ga.final_pos = fin.pos;
+  ga.final_tf = fin.tf;
+  ga.n_elem = n_elem;
+  ga.back = static_cast<uint32_t>(c.H.back);
+  ga.probe = c.k.gen_probe;
+  if (tail_fin) ga.tail_fin = 1u, ga.fin_lo = fin.fin_lo, ga.next_lo = fin.next_lo;
+  ga.sub_n = ga.S + (tail_fin ? 0u : 1u);  // + the final-state wave
+  return ga;
+}
+
+// The device's speculation state, held for the call through `hold` (null:
+// none, or another thread's call holds it).
+SpecState* spec_try_hold(std::unique_lock<std::mutex>& hold) {
+  int dev = 0;
+  SpecState* sp = hipGetDevice(&dev) == hipSuccess ? spec_slot(dev) : nullptr;
+  if (sp) hold = std::unique_lock<std::mutex>(sp->m, std::try_to_lock);
+  return sp && hold.owns_lock() ? sp : nullptr;
+}
+
+// The device draw of n_elem * tm1 coefficients from CPython state
+// (mt_state, *mt_index): the plan (mt_plan.hpp), the call's state to the
+// device, its jump levels unless the previous call speculated them, then
+// `launch_gen(ga, stream, knobs)` (the generation kernel: coefficients or
+// fused split) by one of the four paths above, then CPython's final state.
 template <typename F>
 int mt_device_run(const char* name, uint32_t* mt_state, int32_t* mt_index, uint64_t n_elem, int tm1, void* scratch,
                   uint64_t scratch_bytes, void* stream, int ring_units, F launch_gen) {
@@ -2169,35 +1981,17 @@ int mt_device_run(const char* name, uint32_t* mt_state, int32_t* mt_index, uint6
   if (S > mt_jump_max_subs() - 1)
     return set_error(DN_ERR_UNSUPPORTED, "%s: %llu words exceed the jump table", name,
                      static_cast<unsigned long long>(17 * ncoef));
-  if (scratch_bytes < dn_mt19937_device_scratch_bytes(n_elem, tm1)) return set_error(DN_ERR_ARG, "%s: scratch too small", name);
+  if (scratch_bytes < mt_scratch_bytes(ncoef)) return set_error(DN_ERR_ARG, "%s: scratch too small", name);
 
-  // CPython's state after the draw: the array at buffer position tf = 624 q,
-  // stepped by the final-state wave from window `sig` (position P_sig < tf)
-  const uint64_t words = 17 * ncoef, h = static_cast<uint64_t>(kMtN - idx);
-  int32_t sig = -1, fidx = idx + static_cast<int32_t>(words <= h ? words : 0);
-  uint64_t fpos = 0, ftf = 0;
-  if (words > h) {
-    const uint64_t m_end = words - h, q = (m_end + kMtN - 1) / kMtN, tf = kMtN * q;
-    const uint64_t Lk = 17 * mt_sub_draws(mt_sub_len(ncoef));  // words per substream
-    uint64_t sg = (tf + kMtN - 1 - static_cast<uint64_t>(idx)) / Lk;  // idx + sg L - 624 < tf
-    if (sg > S - 1) sg = S - 1;
-    sig = static_cast<int32_t>(sg);
-    fpos = sg ? static_cast<uint64_t>(idx) + sg * Lk - kMtN : 0;
-    ftf = tf;
-    fidx = static_cast<int32_t>(m_end - kMtN * (q - 1));
-  }
-
-  // scratch: head (flag at 0, final array at 256) | W_idx (the caller's
-  // array advanced idx words: window "-1", the level-A source) | windows 0..S
-  // (row 0 the caller's array; row S unused) | part rows (split levels).  The
-  // job tables are the device copy of this shape's (device_jobs).  What the
-  // GPU needs from the host is the prefix head .. row 0: ONE copy from the
-  // pinned staging buffer, which holds that prefix and, in its tail, the head
-  // read back at the end.
+  const MtKnobs k = mt_knobs();
   const int ki = mt_sub_len(ncoef);
+  const MtFinal fin = mt_final_plan(idx, ncoef, S, ki);
+  const bool tail_fin = fin.sig >= 0 && k.tail_fin;
   MtHost& H = mt_levels(S, ki);
-  const Level* lv = H.lv;
-  const uint64_t njobs = lv[0].jobs.size() + lv[1].jobs.size() + lv[2].jobs.size();
+  // The job tables are the device copy of this shape's (device_jobs).  What
+  // the GPU needs from the host is the scratch prefix head .. row 0: ONE copy
+  // from the pinned staging buffer, which holds that prefix and, in its tail,
+  // the head the generation writes (flag, final array).
   int jerr = 0;
   const void* jobs_dev = device_jobs(H, &jerr);
   if (jerr) return set_error(DN_ERR_HIP, "%s: job tables on the device", name);
@@ -2212,379 +2006,129 @@ int mt_device_run(const char* name, uint32_t* mt_state, int32_t* mt_index, uint6
   mt_advance_window(mt_state, static_cast<uint64_t>(idx), stw);  // W_idx
   std::memcpy(stw + kMtN, mt_state, kMtN * 4);                    // row 0
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // DN_MT_SPEC_PROBE (tuning build, timing probe only: the output is wrong):
-  // 1 = the call's jump levels skipped (the generation reads stale windows);
-  // 2 = skipped, and the same levels run on the side stream into a buffer of
-  // their own, launched before the generation and awaited by the next call's
-  // generation — the cost of a next call's speculative levels beside this
-  // call's generation; 3 = as 2, launched after the generation; 4 = as 2 with
-  // the runtime direct level by mt_jumpc_kernel<4, 2> (beside the generation);
-  // 5 = the call's own levels by mt_jumpc_kernel<4, 2> (its time alone).
-  const char* spp = tune_env("DN_MT_SPEC_PROBE");
-  const int spec_probe = spp ? std::atoi(spp) : 0;
-  // the speculation state (DN_MT_SPEC): this call's draw may have been
-  // speculated (hit), and it may speculate on the next one (spec_next)
-  const char* spe = tune_env("DN_MT_SPEC");
-  // DN_MT_TAIL_FIN (default 1; tuning build: 0 = the final-state wave)
-  const char* tfe = tune_env("DN_MT_TAIL_FIN");
-  const bool tail_fin = sig >= 0 && (tfe ? tfe[0] != '0' : DN_MT_TAIL_FIN != 0);
-  const char* spm = tune_env("DN_MT_SPEC_MIN");
-  const uint64_t spec_min = spm ? std::strtoull(spm, nullptr, 10) : DN_MT_SPEC_MIN;
-  const char* bmn = tune_env("DN_MT_BESIDE_MIN");
-  const uint64_t beside_min = bmn ? std::strtoull(bmn, nullptr, 10) : DN_MT_BESIDE_MIN;
-  const bool spec_on = (spe ? spe[0] != '0' : DN_MT_SPEC != 0) && spec_probe == 0 && !H.split2 && tail_fin &&
-                       njobs > 0 && ncoef >= std::min(spec_min, beside_min);
-  SpecState* sp = nullptr;
+
+  // the speculation state: this call's draw may have been speculated (hit),
+  // and it may speculate on the next one (spec_next)
+  const bool spec_on = k.spec && !k.own_by_jumpc && !H.split2 && tail_fin && S >= 2 &&  // (S >= 2: there are levels)
+                       ncoef >= std::min(k.spec_min, k.beside_min);
   std::unique_lock<std::mutex> spl;
-  if (spec_on) {
-    int dev = 0;
-    if (hipGetDevice(&dev) == hipSuccess && (sp = spec_slot(dev))) {
-      spl = std::unique_lock<std::mutex>(sp->m, std::try_to_lock);
-      if (!spl.owns_lock()) sp = nullptr;
-    }
-  }
-  bool hit = false, spec_next = false, widx2 = false;
-  if (sp) {
-    // this call continues the previous one (same size, starting where it
-    // ended): a hit if that call speculated, and a reason to speculate again
-    const bool cont = sp->have_end && sp->ncoef == ncoef && sp->idx == idx &&
-                      !std::memcmp(sp->state, mt_state, kMtN * 4);
-    hit = cont && sp->armed;
-    if (sp->armed && !hit) ++sp->misses;
-    widx2 = hit && sp->widx2;
-    sp->armed = false;
-    sp->widx2 = false;
-    sp->have_end = false;
-    spec_next = cont && spec_buffers(*sp, dn_mt19937_device_scratch_bytes(n_elem, tm1));
-  }
-  // beside (DN_MT_SPEC_BESIDE, runtime direct level only): the next call's
-  // W_idx by one jump from this call's, then its level, both by
-  // mt_jumpc_kernel<4, 2> on the side stream beside this call's generation
-  // Other shapes: the levels as they are (mt_jump_kernel, 83 KB workgroups)
-  // when the generation's rings leave a CU that much LDS (a generation of at
-  // most ~1000 3-of-5 substreams: 2^22 coefficients and less), and when the
-  // generation outlasts them: substreams of 2^12 draws, or of 2^10 and at most
-  // 256 of them (loops of 2^20 / 2^16 elements -15 / -10 %; 512 substreams
-  // of 2^10 draws, 2^18 elements, +2.5 %: profiles/r06/y/).
-  const char* sbe = tune_env("DN_MT_SPEC_BESIDE");
-  const uint64_t gen_lds = (1u + 2u * 17u * 64u * static_cast<uint32_t>(ring_units) + 64u) * 4u;
-  const bool levels_fit = (S + kCus - 1) / kCus * gen_lds + (kEWords + kMtN + 64) * 4u <= kLdsPerCu;
-  const bool beside = spec_next && (sbe ? sbe[0] != '0' : DN_MT_SPEC_BESIDE != 0) && ncoef >= beside_min &&
-                      (H.rt ? !H.beside.jobs.empty() : levels_fit && (mt_sub_draws(ki) >= 4096 || S <= 256)) &&
-                      !H.j0.jobs.empty() && spec_xpow(*sp, words);
-  if (!beside && ncoef < spec_min) spec_next = false;  // (no speculation after the generation this small)
-  const int spec_dst = sp ? sp->next ^ 1 : 0;  // the buffer the next call's windows go to
+  SpecState* sp = spec_on ? spec_try_hold(spl) : nullptr;
+  const SpecPlan p = spec_decide(sp, k, H, ncoef, ring_units, idx, mt_state);
   // a hit generates from its speculated buffer; a beside call runs in the
   // other library buffer too (the side stream reads its W_idx from there)
-  uint8_t* sc = hit || beside ? static_cast<uint8_t*>(sp->buf[sp->next]) : static_cast<uint8_t*>(scratch);
-  const JumpJob* djobs = static_cast<const JumpJob*>(jobs_dev);
-  const CombineJob* dcomb = reinterpret_cast<const CombineJob*>(djobs + njobs);
-  uint32_t* dwin = reinterpret_cast<uint32_t*>(sc + kHead) + kMtN;  // row 0
+  uint8_t* sc = p.hit || p.beside ? static_cast<uint8_t*>(sp->buf[sp->next]) : static_cast<uint8_t*>(scratch);
   // the side stream's last work (the speculated levels) is done before this
   // call writes a speculation buffer or reads one (a wait on the device only
   // if it is still running)
-  hipError_t err = (spec_next || hit) && hipEventQuery(sp->done) != hipSuccess ? hipStreamWaitEvent(s, sp->done, 0)
-                                                                              : hipSuccess;
-  if (err == hipSuccess && (spec_next || hit) && hipEventQuery(sp->done2) != hipSuccess)
+  hipError_t err = (p.spec_next || p.hit) && hipEventQuery(sp->done) != hipSuccess ? hipStreamWaitEvent(s, sp->done, 0)
+                                                                                   : hipSuccess;
+  if (err == hipSuccess && (p.spec_next || p.hit) && hipEventQuery(sp->done2) != hipSuccess)
     err = hipStreamWaitEvent(s, sp->done2, 0);
   if (err == hipSuccess) err = hipMemcpyAsync(sc, pin, wpre * 4, hipMemcpyHostToDevice, s);
   if (err != hipSuccess) {
     (void)hipStreamSynchronize(s);  // the staging buffer is reused by the next call
     return set_error(DN_ERR_HIP, "%s: %s", name, hipGetErrorString(err));
   }
-  SideStream* side = H.split2 || spec_probe >= 2 ? side_stream() : nullptr;
-  if ((H.split2 || spec_probe >= 2) && !side) {
+  SideStream* side = H.split2 ? side_stream() : nullptr;
+  if (H.split2 && !side) {
     (void)hipStreamSynchronize(s);
     return set_error(DN_ERR_HIP, "%s: side stream", name);
   }
-  auto launch_levels = [&](hipStream_t ls, uint32_t* wins) {
-    uint64_t off = 0, coff = 0;
-    for (int k = 0; k < 3; ++k) {
-      const Level& l = lv[k];
-      if (!l.jobs.empty()) {
-        const char* jpr = tune_env("DN_MT_JUMP_PROBE");
-        const JumpArgs ja{wins, djobs + off, static_cast<uint32_t>(l.jobs.size()),
-                          jpr ? static_cast<uint32_t>(std::atoi(jpr)) : 0u, rt_dev};
-        const dim3 grid(static_cast<uint32_t>(l.jobs.size() / static_cast<size_t>(l.W)));
-        const char* j4 = tune_env("DN_MT_JUMP4B");  // tuning build: 16-wave levels by mt_jumpc_kernel<16, 4>
-        if (l.W == 16 && j4 && j4[0] == '1') hipLaunchKernelGGL((mt_jumpc_kernel<16, 4>), grid, dim3(64 * 16), 0, ls, ja);
-        else if (l.W == 16) hipLaunchKernelGGL(mt_jump_kernel<16>, grid, dim3(64 * 16), 0, ls, ja);
-        else hipLaunchKernelGGL(mt_jump_kernel<8>, grid, dim3(64 * 8), 0, ls, ja);
-      }
-      if (!l.comb.empty())
-        hipLaunchKernelGGL(mt_combine_kernel, dim3(static_cast<uint32_t>(l.comb.size())), dim3(640), 0, ls, wins,
-                           dcomb + coff);
-      off += l.jobs.size();
-      coff += l.comb.size();
-      // split2: the first half's windows are complete after level 0
-      if (H.split2 && k == 0) err = hipEventRecord(side->levels, ls);
-    }
-  };
-  auto probe_beside = [&](hipStream_t ls, uint32_t* wins) {  // DN_MT_SPEC_PROBE=4: the rt level by mt_jumpc_kernel<4, 2>
-    const Level& l = H.beside;
-    if (l.jobs.empty()) return;
-    const JumpJob* bj = reinterpret_cast<const JumpJob*>(static_cast<const uint32_t*>(jobs_dev) + H.beside_off);
-    const JumpArgs ja{wins, bj, static_cast<uint32_t>(l.jobs.size()), 0u, rt_dev};
-    launch_jumpc4(dim3(static_cast<uint32_t>(l.jobs.size() / 4)), ls, ja);
-  };
-  auto probe_levels = [&]() {
-    if (!side->buf || side->buf_bytes < scratch_bytes) {
-      if (side->buf) (void)hipFree(side->buf);
-      side->buf = nullptr;
-      side->buf_bytes = 0;
-      if (hipMalloc(&side->buf, scratch_bytes) != hipSuccess) return hipErrorOutOfMemory;
-      side->buf_bytes = scratch_bytes;
-    }
-    hipError_t e = hipStreamWaitEvent(side->s, side->copy, 0);
-    uint32_t* pw = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(side->buf) + kHead) + kMtN;
-    if (spec_probe == 4) probe_beside(side->s, pw);
-    else launch_levels(side->s, pw);
-    if (e == hipSuccess) e = hipEventRecord(side->spec, side->s);
-    side->pending = true;
-    return e;
-  };
-  if (spec_probe == 5) {
-    probe_beside(s, dwin);
-  } else if (spec_probe == 0) {
-    if (!hit) launch_levels(s, dwin);  // (a hit's windows are in place)
-  } else if (spec_probe >= 2) {
-    err = hipEventRecord(side->copy, s);
-    if (err == hipSuccess && side->pending) err = hipStreamWaitEvent(s, side->spec, 0);
-    if (err == hipSuccess && (spec_probe == 2 || spec_probe == 4)) err = probe_levels();
-  }
-  GenArgs ga{};
-  ga.wins = dwin;
-#if DN_MT_HOST_HEAD
-  head[0] = 0u;  // the flag; the final-state wave writes the final array at head + 64
+  const MtCall c{k, H, s, sc, reinterpret_cast<uint32_t*>(sc + kHead) + kMtN, jobs_dev, rt_dev, sp, side};
+  if (k.own_by_jumpc) launch_beside_level(c, s, c.dwin);
+  else if (!p.hit) err = launch_levels(c, s, c.dwin, H.split2 ? side->levels : nullptr);  // (a hit's windows are in place)
+
+  // The generation writes the flag and CPython's final array straight into
+  // the staging buffer's tail (mapped host memory, visible once the stream has
+  // synchronised): no read-back copy (make_shares_vec 2^12 -1.5 us, profiles/r04/e/)
+  head[0] = 0u;
   void* dhead = nullptr;
   if (hipHostGetDevicePointer(&dhead, head, 0) != hipSuccess || !dhead) {
     (void)hipStreamSynchronize(s);
     return set_error(DN_ERR_HIP, "%s: staging buffer not mapped", name);
   }
-  ga.flag = static_cast<uint32_t*>(dhead);
-  ga.fin = static_cast<uint32_t*>(dhead) + 64;
-#else
-  ga.flag = reinterpret_cast<uint32_t*>(sc);
-  ga.fin = reinterpret_cast<uint32_t*>(sc + 256);
-#endif
-  ga.ncoef = ncoef;
-  ga.sub_draws = mt_sub_draws(ki);
-  ga.vb = dn_m521_vec_bytes(n_elem);
-  ga.tm1_magic = ((1ull << 32) + static_cast<uint64_t>(tm1) - 1) / static_cast<uint64_t>(tm1);
-  ga.S = static_cast<uint32_t>(S);
-  ga.idx = static_cast<uint32_t>(idx);
-  ga.tm1 = tm1;
-  ga.final_sig = sig;
-  ga.final_pos = fpos;
-  ga.final_tf = ftf;
-  ga.n_elem = n_elem;
-  ga.back = static_cast<uint32_t>(H.back);
-  const char* pr = tune_env("DN_MT_PROBE");
-  ga.probe = pr ? static_cast<uint32_t>(std::atoi(pr)) : 0u;
-  if (tail_fin) {
-    // the last substream's frame: position 0 = stream position idx + (S - 1) L
-    const uint64_t base = static_cast<uint64_t>(idx) + (S - 1) * (17 * mt_sub_draws(ki));
-    ga.tail_fin = 1u;
-    ga.fin_lo = static_cast<int32_t>(static_cast<int64_t>(ftf) - static_cast<int64_t>(base));
-    ga.next_lo = static_cast<int32_t>(static_cast<int64_t>(idx + words) - static_cast<int64_t>(base));
-  }
-  const uint32_t nwg = static_cast<uint32_t>(S) + (tail_fin ? 0u : 1u);  // + the final-state wave
-  ga.sub_n = nwg;
-  bool side_used = false;  // work of this call on the speculation side stream
-  if (H.split2) {
-    // substreams [0, S/2) on the side stream once level 0 is done (beside
-    // level 1's jumps), then [S/2, S] and the final-state wave on the call's
-    // stream after level 1; the call's stream then waits for the side stream
-    const uint32_t half = static_cast<uint32_t>(mt_split_half(S));
-    if (err == hipSuccess) err = hipStreamWaitEvent(side->s, side->levels, 0);
-    GenArgs g1 = ga;
-    g1.sub_lo = 0u;
-    g1.sub_n = half;
-    launch_gen(g1, side->s);
-    if (err == hipSuccess) err = hipEventRecord(side->gen, side->s);
-    ga.sub_lo = half;
-    ga.sub_n = nwg - half;
-    launch_gen(ga, s);
-    if (err == hipSuccess) err = hipStreamWaitEvent(s, side->gen, 0);
-  } else if (beside) {
-    // Once this call's windows are in place, in workgroups of 11 KB that fit
-    // on a CU beside the generation's rings: on the side stream the next
-    // call's level into the other buffer from its W_idx (row -1 there) — which
-    // the previous call computed (widx2) or, first, one jump by x^(17 ncoef)
-    // from this call's W_idx computes (copied to row S, 32 parts + combine);
-    // on the second side stream the W_idx of the call after that, jumped from
-    // the next call's into this call's buffer (rows S, part rows and -1: none
-    // of them read by this call's generation).
-    uint8_t* nb = static_cast<uint8_t*>(sp->buf[spec_dst]);
-    uint32_t* nw = reinterpret_cast<uint32_t*>(nb + kHead) + kMtN;  // the next call's row 0
-    const uint32_t* hj = static_cast<const uint32_t*>(jobs_dev);
-    auto jump0 = [&](hipStream_t ls, uint32_t* w) {  // row S -> row -1 of w by x^(17 ncoef)
-      const JumpArgs j0{w, reinterpret_cast<const JumpJob*>(hj + H.j0_off), static_cast<uint32_t>(H.j0.jobs.size()), 0u,
-                        sp->xpow};
-      launch_jumpc4(dim3(static_cast<uint32_t>(H.j0.jobs.size() / 4)), ls, j0);
-      hipLaunchKernelGGL(mt_combine_kernel, dim3(static_cast<uint32_t>(H.j0.comb.size())), dim3(640), 0, ls, w,
-                         reinterpret_cast<const CombineJob*>(hj + H.j0_comb_off));
-    };
-    err = hipEventRecord(sp->win, s);
-    launch_gen(ga, s);
-    side_used = true;
-    if (err == hipSuccess) err = hipStreamWaitEvent(sp->side, sp->win, 0);
-    if (err == hipSuccess) err = hipStreamWaitEvent(sp->side2, sp->win, 0);
-    if (!widx2) {
-      if (err == hipSuccess)
-        err = hipMemcpyAsync(nw + S * kMtN, dwin - kMtN, kMtN * 4, hipMemcpyDeviceToDevice, sp->side);
-      jump0(sp->side, nw);
-      if (err == hipSuccess) err = hipEventRecord(sp->j0ev, sp->side);
-      if (err == hipSuccess) err = hipStreamWaitEvent(sp->side2, sp->j0ev, 0);
-    }
-    if (H.rt) {
-      const JumpArgs bl{nw, reinterpret_cast<const JumpJob*>(hj + H.beside_off),
-                        static_cast<uint32_t>(H.beside.jobs.size()), 0u, rt_dev};
-      launch_jumpc4(dim3(static_cast<uint32_t>(H.beside.jobs.size() / 4)), sp->side, bl);
-    } else {
-      launch_levels(sp->side, nw);
-    }
-    if (err == hipSuccess) err = hipEventRecord(sp->done, sp->side);
-    if (err == hipSuccess)
-      err = hipMemcpyAsync(dwin + S * kMtN, nw - kMtN, kMtN * 4, hipMemcpyDeviceToDevice, sp->side2);
-    jump0(sp->side2, dwin);
-    if (err == hipSuccess) err = hipEventRecord(sp->done2, sp->side2);
-    ++sp->launched;
-  } else if (spec_next) {
-    // the generation, whose last substream also writes the next call's W_idx
-    // into row -1 of the other buffer; then on the side stream the next
-    // call's jump levels from it, while this call's host side finishes and
-    // the next call's begins
-    uint8_t* nb = static_cast<uint8_t*>(sp->buf[spec_dst]);
-    ga.next_win = reinterpret_cast<uint32_t*>(nb + kHead);
-    launch_gen(ga, s);
-    err = hipEventRecord(sp->win, s);
-    if (err == hipSuccess) err = hipStreamWaitEvent(sp->side, sp->win, 0);
-    side_used = true;
-    launch_levels(sp->side, reinterpret_cast<uint32_t*>(nb + kHead) + kMtN);
-    if (err == hipSuccess) err = hipEventRecord(sp->done, sp->side);
-    ++sp->launched;
-  } else {
-    launch_gen(ga, s);
-    if (err == hipSuccess && spec_probe == 3) err = probe_levels();
-  }
+  GenArgs ga = gen_args(c, fin, tail_fin, idx, n_elem, tm1, static_cast<uint32_t*>(dhead));
+  auto gen = [&](GenArgs& g, hipStream_t gs) { launch_gen(g, gs, k); };
+  const MtLaunched r = H.split2      ? run_split2(c, ga, gen, err)
+                       : p.beside    ? run_beside(c, p, ga, gen)
+                       : p.spec_next ? run_spec_after(c, p, ga, gen)
+                                     : run_plain(c, ga, gen, err);
+  err = r.err;
   // an early exit waits for this call's side work too (it writes the staging buffer)
-  auto drain = [&]() {
-    (void)hipStreamSynchronize(s);
-    if (side_used) (void)hipStreamSynchronize(sp->side), (void)hipStreamSynchronize(sp->side2);
+  auto drain_side = [&]() {
+    if (r.side_used) (void)hipStreamSynchronize(sp->side), (void)hipStreamSynchronize(sp->side2);
   };
   if (err != hipSuccess) {
-    drain();
+    (void)hipStreamSynchronize(s);
+    drain_side();
     return set_error(DN_ERR_HIP, "%s: side stream: %s", name, hipGetErrorString(err));
   }
   err = hipGetLastError();
   if (err != hipSuccess) {
-    drain();
+    (void)hipStreamSynchronize(s);
+    drain_side();
     return set_error(DN_ERR_HIP, "%s: launch: %s", name, hipGetErrorString(err));
   }
-
-#if !DN_MT_HOST_HEAD
-  err = hipMemcpyAsync(head, sc, wh * 4, hipMemcpyDeviceToHost, s);  // flag .. final array
-#endif
-  const hipError_t serr = mt_wait(s);
-  if (err == hipSuccess) err = serr;
+  err = hipStreamSynchronize(s);
   if (err != hipSuccess) {
-    if (side_used) (void)hipStreamSynchronize(sp->side), (void)hipStreamSynchronize(sp->side2);
+    drain_side();
     return set_error(DN_ERR_HIP, "%s: %s", name, hipGetErrorString(err));
   }
-  if (hit) ++sp->hits;
-  // DN_MT_FORCE_RETRY=1 (tuning build) takes the rejected-draw exit so the
-  // caller's host fallback can be exercised.
-  const char* fr = tune_env("DN_MT_FORCE_RETRY");
-  if (head[0] || (fr && fr[0] == '1')) return set_error(DN_ERR_RETRY, "%s: a draw was rejected; redo on the host", name);
-  if (sig >= 0) std::memcpy(mt_state, head + 256 / 4, kMtN * 4);
-  *mt_index = fidx;
-  if (sp) {
-    // where this call ended; the next call, if it starts here, uses the
-    // speculated windows (spec_next) or speculates itself
-    sp->have_end = true;
-    sp->ncoef = ncoef;
-    sp->idx = fidx;
-    std::memcpy(sp->state, mt_state, kMtN * 4);
-    sp->armed = spec_next;
-    sp->widx2 = beside;  // this call's buffer now holds the W_idx after the next call's
-    if (spec_next) sp->next = spec_dst;
-  }
+  if (p.hit) ++sp->hits;
+  if (head[0] || k.force_retry) return set_error(DN_ERR_RETRY, "%s: a draw was rejected; redo on the host", name);
+  if (fin.sig >= 0) std::memcpy(mt_state, head + 256 / 4, kMtN * 4);
+  *mt_index = fin.fidx;
+  if (sp) spec_record_end(*sp, p, ncoef, fin.fidx, mt_state);
   return DN_OK;
 }
 
-#ifndef DN_MT_SAUX
-#define DN_MT_SAUX 16
-#endif
-constexpr int kSc1 = DN_MT_SAUX;
-// the fused split's generation and emission on two waves per substream for
-// draws of few substreams (mt_gen_pc_kernel; 0: always one wave, mt_gen_kernel)
-#ifndef DN_MT_PC
-#define DN_MT_PC 1
-#endif  // buffer-store cache policy of the 3-of-5 share stores: sc1 (16)
+// buffer-store cache policy of the 3-of-5 share stores: sc1 (16) rather than
+// non-temporal: 2.2 % faster on two buffers of one process
+// (profiles/r03/ab/mt_store_aux_ns5.json)
+constexpr int kSc1 = 16;
 
+// The generation kernel of a call.  The headline 3-of-5: straight-line share
+// stores (see mt_gen_kernel).  Generation and emission on two waves per
+// substream (mt_gen_pc_kernel): at 2^24 the kernel runs at its emission-only
+// time (0.92 vs 1.01 ms for the one-wave kernel on a share block,
+// profiles/r04/t/), at 2^20 / 2^16 / 2^12 make_shares_vec -12 / -8 / -3 %
+// (profiles/r04/l/); the one-wave kernel (mt_gen_kernel) is the tuning
+// build's A/B (MtKnobs::pc).
 // SEG: the segmented emission (ga.segs; dn_mt19937_split_many_device)
 template <int T, bool SEG = false>
-void launch_gen(GenArgs& ga, hipStream_t s) {
+void launch_gen(GenArgs& ga, hipStream_t s, const MtKnobs& k) {
   ga.ring = 2u * 17u * 64u * (T ? T - 1 : 1);
   const uint32_t lds_words = 1u + ga.ring + 64u;  // GenRing: alignment word, ring, mirror
-#ifdef DN_TUNING
-  // DN_MT_STORE_AUX (tuning build): cache policy bits of the fused split's share stores (3-of-5)
-  const char* sa = T == 3 ? tune_env("DN_MT_STORE_AUX") : nullptr;
-  if (sa && T == 3 && ga.n_shares == 5 && !SEG) {
-    const int aux = std::atoi(sa);
-    constexpr int NS = T == 3 ? 5 : 0;
-    const dim3 g(ga.S + 1), b(64);
-    if (aux == 0) hipLaunchKernelGGL((mt_gen_kernel<T, 0, NS>), g, b, lds_words * 4u, s, ga);
-    else if (aux == 1) hipLaunchKernelGGL((mt_gen_kernel<T, 1, NS>), g, b, lds_words * 4u, s, ga);
-    else if (aux == 2) hipLaunchKernelGGL((mt_gen_kernel<T, 2, NS>), g, b, lds_words * 4u, s, ga);
-    else if (aux == 16) hipLaunchKernelGGL((mt_gen_kernel<T, 16, NS>), g, b, lds_words * 4u, s, ga);
-    else hipLaunchKernelGGL((mt_gen_kernel<T, 18, NS>), g, b, lds_words * 4u, s, ga);
-    return;
+  uint32_t grid = ga.sub_n ? ga.sub_n : ga.S + 1;
+  if (k.pc) {
+    if (k.gen_subs) grid = std::min(grid, k.gen_subs);
+    if (T == 3 && ga.n_shares == 5)
+      hipLaunchKernelGGL((mt_gen_pc_kernel<T, kSc1, T == 3 ? 5 : 0, SEG>), dim3(grid), dim3(128), lds_words * 4u, s, ga);
+    else
+      hipLaunchKernelGGL((mt_gen_pc_kernel<T, kNt, 0, SEG>), dim3(grid), dim3(128), lds_words * 4u, s, ga);
+  } else if (T == 3 && ga.n_shares == 5) {
+    hipLaunchKernelGGL((mt_gen_kernel<T, kSc1, T == 3 ? 5 : 0, SEG>), dim3(grid), dim3(64), lds_words * 4u, s, ga);
+  } else {
+    hipLaunchKernelGGL((mt_gen_kernel<T, kNt, 0, SEG>), dim3(grid), dim3(64), lds_words * 4u, s, ga);
   }
-#endif
-  // the headline 3-of-5: straight-line share stores (see mt_gen_kernel), sc1
-  // rather than non-temporal: 2.2 % faster on two buffers of one process
-  // (profiles/r03/ab/mt_store_aux_ns5.json)
-  // Generation and emission on two waves per substream (mt_gen_pc_kernel):
-  // at 2^24 the kernel runs at its emission-only time (0.92 vs 1.01 ms for
-  // the one-wave kernel on a share block, profiles/r04/t/), at 2^20 / 2^16 /
-  // 2^12 make_shares_vec -12 / -8 / -3 % (profiles/r04/l/).
-  if constexpr (DN_MT_PC) {
-    // DN_MT_PC_FORCE (tuning build): 0 = the one-wave kernel (A/B)
-    const char* pf = tune_env("DN_MT_PC_FORCE");
-    const bool pc = !(pf && pf[0] == '0');
-    // DN_MT_GEN_SUBS (tuning build, timing probe only: the output is partial and
-    // CPython's final state is not computed): launch only the first K substream
-    // workgroups — how the generation's time scales with the substreams in flight
-    uint32_t grid = ga.sub_n ? ga.sub_n : ga.S + 1;
-    if (const char* gs = tune_env("DN_MT_GEN_SUBS")) grid = std::min<uint32_t>(grid, std::max(1, std::atoi(gs)));
-    if (pc) {
-      if (T == 3 && ga.n_shares == 5)
-        hipLaunchKernelGGL((mt_gen_pc_kernel<T, kSc1, T == 3 ? 5 : 0, SEG>), dim3(grid), dim3(128), lds_words * 4u, s,
-                           ga);
-      else
-        hipLaunchKernelGGL((mt_gen_pc_kernel<T, kNt, 0, SEG>), dim3(grid), dim3(128), lds_words * 4u, s, ga);
-      return;
-    }
-  }
-  const dim3 g1(ga.sub_n ? ga.sub_n : ga.S + 1);
-  if (T == 3 && ga.n_shares == 5)
-    hipLaunchKernelGGL((mt_gen_kernel<T, kSc1, T == 3 ? 5 : 0, SEG>), g1, dim3(64), lds_words * 4u, s, ga);
-  else
-    hipLaunchKernelGGL((mt_gen_kernel<T, kNt, 0, SEG>), g1, dim3(64), lds_words * 4u, s, ga);
 }
 
 }  // namespace
 }  // namespace dn
 
+using namespace dn;
+
+extern "C" uint64_t dn_mt19937_device_scratch_bytes(uint64_t n_elem, int tm1) {
+  return mt_scratch_bytes(tm1 > 0 ? n_elem * static_cast<uint64_t>(tm1) : 0);
+}
+
 extern "C" int dn_mt19937_draw_coeffs_device(uint32_t* mt_state, int32_t* mt_index, uint64_t n_elem, int tm1,
                                              void* coeffs, void* scratch, uint64_t scratch_bytes, void* stream) {
   if (n_elem && tm1 > 0 && !coeffs) return set_error(DN_ERR_ARG, "dn_mt19937_draw_coeffs_device: null pointer");
   return mt_device_run("dn_mt19937_draw_coeffs_device", mt_state, mt_index, n_elem, tm1, scratch, scratch_bytes, stream, 1,
-                       [&](GenArgs& ga, hipStream_t s) {
+                       [&](GenArgs& ga, hipStream_t s, const MtKnobs& k) {
                          ga.coeffs = static_cast<uint8_t*>(coeffs);
-                         launch_gen<0>(ga, s);
+                         launch_gen<0>(ga, s, k);
                        });
 }
 
@@ -2609,13 +2153,13 @@ extern "C" int dn_mt19937_split_device(uint32_t* mt_state, int32_t* mt_index, co
                      name, threshold, n_shares);
   if (n_elem && (!secrets || !shares)) return set_error(DN_ERR_ARG, "%s: null pointer", name);
   return mt_device_run(name, mt_state, mt_index, n_elem, threshold - 1, scratch, scratch_bytes, stream, threshold - 1,
-                       [&](GenArgs& ga, hipStream_t s) {
+                       [&](GenArgs& ga, hipStream_t s, const MtKnobs& k) {
                          ga.secrets = secrets;
                          ga.shares = static_cast<uint8_t*>(shares);
                          ga.n_shares = n_shares;
-                         if (threshold == 2) launch_gen<2>(ga, s);
-                         else if (threshold == 3) launch_gen<3>(ga, s);
-                         else launch_gen<5>(ga, s);
+                         if (threshold == 2) launch_gen<2>(ga, s, k);
+                         else if (threshold == 3) launch_gen<3>(ga, s, k);
+                         else launch_gen<5>(ga, s, k);
                        });
 }
 
@@ -2685,14 +2229,14 @@ extern "C" int dn_mt19937_split_many_device(uint32_t* mt_state, int32_t* mt_inde
     return set_error(DN_ERR_HIP, "%s: segment table upload", name);
   }
   const int rc = mt_device_run(name, mt_state, mt_index, n_total, tm1, scratch, draw_bytes, stream, tm1,
-                               [&](GenArgs& ga, hipStream_t s) {
+                               [&](GenArgs& ga, hipStream_t s, const MtKnobs& k) {
                                  ga.secrets = secrets;
                                  ga.n_shares = n_shares;
                                  ga.segs = dtab;
                                  ga.nseg = nseg;  // (after mt_device_run's ga.vb: the same storage)
-                                 if (threshold == 2) launch_gen<2, true>(ga, s);
-                                 else if (threshold == 3) launch_gen<3, true>(ga, s);
-                                 else launch_gen<5, true>(ga, s);
+                                 if (threshold == 2) launch_gen<2, true>(ga, s, k);
+                                 else if (threshold == 3) launch_gen<3, true>(ga, s, k);
+                                 else launch_gen<5, true>(ga, s, k);
                                });
   // the draw synchronises the stream before DN_OK and DN_ERR_RETRY; an
   // argument error may return before it, with the table's copy in flight

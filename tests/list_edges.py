@@ -36,7 +36,7 @@ THRESHOLDS = (2, 3, 5)
 # ------------------------------------------------------------------ geometry
 def substream_plan(n_total: int, t: int) -> Tuple[int, int, Set[int]]:
     """(draws per substream, S, the set of backward substreams) of the draw of
-    n_total * (t - 1) coefficients.  Mirrors csrc/mt19937_device.hip:
+    n_total * (t - 1) coefficients.  Mirrors csrc/mt_plan.hpp:
     mt_sub_len (2^8 draws up to 65 * 2^8 coefficients, else 2^10, 2^12 from
     2^21, 2^14 from 2^24), mt_subs (S), mt_levels (back = 0 at 2^8 draws, else
     1) and mt_sub_forward (backward: s even, not 0, not the last)."""

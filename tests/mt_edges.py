@@ -238,13 +238,15 @@ def secrets_for(n: int, seed: int = 0) -> List[int]:
 def geometry(n_elem: int, tm1: int, fused: bool):
     """(ncoef, draws per substream D, substreams S, draws per emission group G,
     backward substreams) of the device draw of n_elem * tm1 coefficients, from
-    the constants csrc/mt19937_device.hip states: the header comment, lines 8-10
-    and 21-27 (substreams of 2^k whole draws; k = 14 from 2^24 coefficients, 12
-    from 2^21, else 10), mt_sub_len's comment, lines 88-92 (2^8 draws up to 65 *
-    2^8 = 16640 coefficients), mt_sub_forward's, lines 696-699 (backward: s even,
-    not 0, not the last), mt_levels', lines 1746-1748 (2^8-draw substreams run
-    forward only) and mt_gen_kernel's, lines 1156-1158 (groups of 64 draws, or of
-    64 elements = 64 (t - 1) draws in the fused draw + split)."""
+    the constants the sources state: csrc/mt19937_device.hip's header comment,
+    its "cutting the word stream into S substreams" sentence and its "generation
+    kernel" item (substreams of 2^k whole draws; k = 14 from 2^24 coefficients,
+    12 from 2^21, else 10); in csrc/mt_plan.hpp the comment over mt_sub_len (2^8
+    draws up to 65 * 2^8 = 16640 coefficients), the one over mt_sub_forward
+    (backward: s even, not 0, not the last) and the first comment inside
+    mt_levels (2^8-draw substreams run forward only); and the comment over
+    mt_gen_kernel in csrc/mt19937_device.hip (groups of 64 draws, or of 64
+    elements = 64 (t - 1) draws in the fused draw + split)."""
     ncoef = n_elem * tm1
     if ncoef <= 65 << 8:
         D, back = 1 << 8, False

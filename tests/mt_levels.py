@@ -1,7 +1,7 @@
 """A plain-Python model of the device MT19937 draw's jump-level builder.
 
-The host code between mt_sub_len and mt_device_run in
-csrc/mt19937_device.hip turns a coefficient count into a substream length, a
+The draw's host planner, csrc/mt_plan.hpp (included by
+csrc/mt19937_device.hip), turns a coefficient count into a substream length, a
 substream count S and up to three jump levels; S alone decides the kind of
 level, how many parts P every jump is cut into, the word ranges of the parts,
 the workgroup width W (mt_jump_kernel<8> or <16>), the group size `per`, which
@@ -11,7 +11,7 @@ mt_window_needed, the runtime-direct condition of mt_levels, build_levels,
 push_level's P / per / W and part_cuts) for the product defaults, so that
 
   * test_mt_levels_host.py can pin it to the real builder (the host compile
-    tools/mt_levels_check.hip, `dump` mode), and
+    tools/mt_levels_check.cpp, `dump` mode), and
   * test_gpu_mt_levels.py can enumerate every distinct level shape and draw at
     each of them.
 
@@ -161,7 +161,7 @@ def j0_parts() -> int:
 
 
 def final_sig(ncoef: int, idx: int, ki: int, S: int) -> int:
-    """`sig` in mt_device_run: the window CPython's final array is stepped from
+    """`sig` of mt_final_plan (csrc/mt_plan.hpp): the window CPython's final array is stepped from
     (-1: the draw ends inside the caller's array).  It is always the last
     window, S - 1 (test_mt_levels_host.py), which every draw jumps to."""
     words, h = 17 * ncoef, MT_N - idx

@@ -1,7 +1,7 @@
 """The device MT19937 draw at every jump-level shape.
 
-The substream count S alone decides how the host code of
-csrc/mt19937_device.hip builds a draw's jump levels: the kind (none, one
+The substream count S alone decides how the draw's host planner
+(csrc/mt_plan.hpp) builds a draw's jump levels: the kind (none, one
 tabulated direct level, the runtime direct level, radix levels A / C / B), the
 parts P every jump is cut into and their word ranges, the workgroup width W
 (mt_jump_kernel<8> or <16>), the group size `per`, what mt_combine_kernel XORs

@@ -2,7 +2,7 @@
 kernel launches): the net itself, before it judges a kernel.
 
 * every list of tests/list_edges.py puts its edges where it claims to, under
-  the substream geometry mirrored from csrc/mt19937_device.hip — the counts
+  the substream geometry mirrored from csrc/mt_plan.hpp — the counts
   below are conditions of the GPU suite's coverage and are asserted;
 * the Python-integer reference reproduces the reference implementation's own
   fixtures (tests/golden/f1_t3n5.npz, f2_t5n9.npz), cut into tensors;

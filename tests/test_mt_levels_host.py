@@ -2,8 +2,9 @@
 pinned to the real builder, and the builder's own regime boundaries, scratch
 bound and unread table rows.
 
-The real builder is the host code of csrc/mt19937_device.hip compiled by
-tools/mt_levels_check.hip (no GPU needed); its `dump` mode prints, per
+The real builder is csrc/mt_plan.hpp, the draw's host-only planner, compiled
+into tools/mt_levels_check.cpp by the host compiler (no GPU and no HIP
+needed); its `dump` mode prints, per
 substream count and length, what mt_levels built: back, rt, the part rows,
 and per level the jumps n, parts P, waves W, workgroups, the largest
 workgroup, the part rows written, the cut list and the table rows read.  The
@@ -29,15 +30,17 @@ BOUNDARY_S = [2049, 2050, 4095, 4096, 4097, 4098, 8193, 16385, 65537]
 def builders(tmp_path_factory):
     """The tool built as the tuning library is (-DDN_TUNING: the DN_* knobs
     apply) and as the product library is (no knob is read), side by side."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
+    cxx = "/opt/rocm/llvm/bin/clang++"
+    if not os.path.exists(cxx):
+        cxx = shutil.which("c++")
+    if not cxx:
+        pytest.skip("no host C++ compiler")
     out = tmp_path_factory.mktemp("mt_levels")
     exes = {"tuning": str(out / "mt_levels_check_tuning"), "product": str(out / "mt_levels_check")}
-    runs = [subprocess.Popen([hipcc, "-O1", "-std=c++17", *(["-DDN_TUNING"] if name == "tuning" else []),
-                              "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"),
+    runs = [subprocess.Popen([cxx, "-O1", "-std=c++17", *(["-DDN_TUNING"] if name == "tuning" else []),
+                              "-I" + os.path.join(ROOT, "include"),
                               "-I" + os.path.join(ROOT, "delta-node_amd", "csrc"),
-                              os.path.join(ROOT, "tools", "mt_levels_check.hip"), "-o", exe],
+                              os.path.join(ROOT, "tools", "mt_levels_check.cpp"), "-o", exe],
                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True) for name, exe in exes.items()]
     for run in runs:
         text = run.communicate()[0]
@@ -281,8 +284,90 @@ def test_shape_census_over_every_supported_size():
     assert max(level[1] for _, _, lv in every for level in lv) == 29
 
 
+def final_plans(exe, pairs):
+    """mt_final_plan's fields, as the builder's `F <idx> <ncoef>` query prints
+    them: {(idx, ncoef): {field: int}}."""
+    text = "".join(f"F {idx} {n}\n" for idx, n in pairs)
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DN_")}
+    r = subprocess.run([exe, "dump"], input=text, capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    out = {}
+    for line in r.stdout.splitlines():
+        assert line.startswith("F "), line
+        f = {k: int(v) for k, v in fields(line).items()}
+        out[(f["idx"], f["ncoef"])] = f
+    assert len(out) == len(set(pairs)), "the builder answered another number of queries"
+    return out
+
+
+def test_final_plan_of_the_builder(builders):
+    """mt_final_plan (csrc/mt_plan.hpp), which mt_device_run takes CPython's
+    state after the draw from.
+
+    The final index against CPython's rule for w = 17 ncoef words drawn at
+    index idx, h = 624 - idx of them left in the caller's array:
+    idx + w if w <= h else (w - h - 1) % 624 + 1 — at idx 0, 1, 333, 623, 624
+    and, for each, the word counts 17, the last w <= h (where one exists), the
+    first w > h, and the w with w - h = 624 m - 1, 624 m, 624 m + 1 (17 is a
+    unit mod 624, so each residue has word counts) for the first such w, the
+    one 624 * 17 words later and one of 2^24-draw size, with the coefficient
+    counts next to each.  sig is -1 exactly while w <= h.
+
+    The window the final array is stepped from, for every substream length
+    and every S of 1, 2, 3, 65, 66, 1025, 2049 a draw of that length can have
+    (2^8 draws: up to 65; 2^10: 17 to 2048; 2^12: 512 to 4096; 2^14: from
+    1024), the last substream holding one draw or full: 0 <= sig <= S - 1, the
+    window is where the model has it, and its position (0: the caller's
+    array, else idx + sig L - 624) lies below the final array's, a multiple of
+    624 at or past the draw's last word."""
+    inv17 = pow(17, -1, ml.MT_N)
+    pairs = set()
+    for idx in (0, 1, 333, 623, 624):
+        h = ml.MT_N - idx
+        ns = {1, h // 17, h // 17 + 1}
+        for r in (-1, 0, 1):
+            n0 = (h + r) * inv17 % ml.MT_N  # 17 n0 - h = r (mod 624)
+            while 17 * n0 <= h:
+                n0 += ml.MT_N
+            big = n0 + ml.MT_N * ((1 << 24) // ml.MT_N)
+            ns |= {n0 - 1, n0, n0 + 1, n0 + ml.MT_N, big - 1, big, big + 1}
+            assert (17 * n0 - h) % ml.MT_N == r % ml.MT_N and (17 * big - h) % ml.MT_N == r % ml.MT_N
+        pairs |= {(idx, n) for n in ns if n >= 1}
+    got = final_plans(builders["product"], sorted(pairs))
+    below = past = 0
+    for (idx, n), f in got.items():
+        w, h = 17 * n, ml.MT_N - idx
+        assert f["fidx"] == (idx + w if w <= h else (w - h - 1) % ml.MT_N + 1), (idx, n, f)
+        assert (f["sig"] == -1) == (w <= h), (idx, n, f)
+        below += w <= h
+        past += w > h and (w - h) % ml.MT_N == 0
+    assert below >= 6 and past >= 15  # (idx 0, 1, 333 have two w <= h each; every idx three w - h = 624 m)
+
+    shapes = [(ki, S) for ki in range(4) for S in (1, 2, 3, 65, 66, 1025, 2049)
+              if ml.supported(S, ki) and (ml.sub_len(ml.coeffs_for(S, ki, True)), ml.subs(ml.coeffs_for(S, ki, True))) == (ki, S)]
+    assert shapes == [(0, 65), (0, 66), (0, 1025), (1, 1025), (1, 2049), (2, 1025), (2, 2049), (3, 1), (3, 2), (3, 3), (3, 65)]
+    pairs = {(idx, ml.coeffs_for(S, ki, full)) for ki, S in shapes for full in (False, True) for idx in (0, 1, 333, 623, 624)}
+    for ki, S in shapes:
+        assert (ml.sub_len(ml.coeffs_for(S, ki, False)), ml.subs(ml.coeffs_for(S, ki, False))) == (ki, S)
+    got = final_plans(builders["product"], sorted(pairs))
+    assert got == final_plans(builders["tuning"], sorted(pairs))
+    for (idx, n), f in got.items():
+        ki, S, L = f["ki"], f["S"], 17 * ml.sub_draws(f["ki"])
+        assert (ki, S) == (ml.sub_len(n), ml.subs(n)) and (ki, S) in shapes
+        w, h = 17 * n, ml.MT_N - idx
+        if w <= h:
+            assert f["sig"] == -1, (idx, n, f)
+            continue
+        assert 0 <= f["sig"] <= S - 1 and f["sig"] == ml.final_sig(n, idx, ki, S), (idx, n, f)
+        assert f["pos"] == (idx + f["sig"] * L - ml.MT_N if f["sig"] else 0), (idx, n, f)
+        assert f["tf"] % ml.MT_N == 0 and f["tf"] - ml.MT_N < w - h <= f["tf"], (idx, n, f)
+        assert f["pos"] < f["tf"], (idx, n, f)
+        # the last substream's frame starts at stream position idx + (S - 1) L
+        assert f["fin_lo"] == f["tf"] - (idx + (S - 1) * L) and f["next_lo"] == idx + w - (idx + (S - 1) * L), (idx, n, f)
+
+
 def test_final_state_window_is_the_last_one():
-    """mt_device_run's `sig`, restated in the model as a closed form, against
+    """mt_final_plan's `sig`, restated in the model as a closed form, against
     a scan over the windows: the largest s <= S - 1 whose window (position
     idx + s L - 624; window 0 the caller's array) starts before CPython's final
     array, the first 624-word array boundary at or past the draw's last word.

@@ -1,6 +1,6 @@
-// mt_levels_check.hip — host check of the MT19937 device draw's jump-job
-// builder (build_levels / push_level in delta-node_amd/csrc/mt19937_device.hip,
-// included here; no GPU needed): for substream counts S up to 300 and the
+// mt_levels_check.cpp — host check of the MT19937 device draw's jump-job
+// builder (build_levels / push_level in delta-node_amd/csrc/mt_plan.hpp, the
+// draw's host-only planner; no GPU and no HIP needed): for substream counts S up to 300 and the
 // boundary sizes up to 65537, for all four substream lengths (2^8 draws: direct levels only) and both
 // generation modes, every window a generation wave starts from (1 .. S-1, or
 // with backward generation the odd ones and S-1: mt_sub_forward) is produced
@@ -13,19 +13,19 @@
 // does for a substream count or a draw size (dump(), below):
 // tests/test_mt_levels_host.py compares tests/mt_levels.py with it.
 //
-// build: hipcc -O1 -std=c++17 --offload-arch=gfx950 -I../include -I../delta-node_amd/csrc mt_levels_check.hip
-#include "mt19937_device.hip"
+// build: clang++ -O1 -std=c++17 -I../include -I../delta-node_amd/csrc mt_levels_check.cpp
+//        (-DDN_TUNING: the planner's DN_MT_* knobs apply, as in the tuning library)
+#include "mt_plan.hpp"
 #include <cstdio>
 #include <map>
 #include <set>
-namespace dn { int set_error(int c, const char*, ...) { return c; } int device_cu_count() { return 256; }
-uint64_t mt_jump_words() { return 0; } uint64_t mt_jump_max_subs() { return 262145; }
-void mt_advance_window(const uint32_t*, uint64_t, uint32_t*) {}
+#include <tuple>
+// the one library function the planner calls
+namespace dn {
 static bool g_rt_rows = false;  // dump mode: the runtime direct rows count as available
 const uint64_t* mt_direct_rows_l14(uint64_t, uint64_t*) { static const uint64_t row = 0; return g_rt_rows ? &row : nullptr; }
-bool mt_xpow_mod(uint64_t, uint64_t*) { return false; } }
+}
 using namespace dn;
-extern "C" uint64_t dn_m521_vec_bytes(uint64_t n) { return n; }
 int check(uint64_t S, int ki, int back, bool rt = false) {
   const bool direct = S - 1 <= static_cast<uint64_t>(kMtDirectRows) || rt;
   // direct rows of this level: the tabulated D_s of length ki, or the runtime rows
@@ -39,16 +39,16 @@ int check(uint64_t S, int ki, int back, bool rt = false) {
   int bad = 0;
   for (size_t k = 0; k < lv.size(); ++k) {
     const Level& L = *lv[k];
-    if (L.jobs.size() % L.W) { printf("S=%llu lvl %d jobs %% W\n", (unsigned long long)S, k); return 1; }
+    if (L.jobs.size() % L.W) { printf("S=%llu lvl %zu jobs %% W\n", (unsigned long long)S, k); return 1; }
     std::map<int, std::tuple<int,int,int,int>> partw;  // row -> (src, poly, lo, hi)
     for (size_t g = 0; g < L.jobs.size(); g += L.W) {
       const JumpJob& j0 = L.jobs[g];
-      if (j0.dst < 0) { printf("S=%llu lvl %d group starts with padding\n", (unsigned long long)S, k); return 1; }
+      if (j0.dst < 0) { printf("S=%llu lvl %zu group starts with padding\n", (unsigned long long)S, k); return 1; }
       for (int w = 0; w < L.W; ++w) {
         const JumpJob& j = L.jobs[g + w];
         if (j.src != j0.src || (j.span & 0xffff) != (j0.span & 0xffff)) { bad++; }
         if (j.dst < 0) continue;
-        if (j.src >= 0 && !known[j.src]) { printf("S=%llu lvl %d src %d unknown\n", (unsigned long long)S, k, j.src); return 1; }
+        if (j.src >= 0 && !known[j.src]) { printf("S=%llu lvl %zu src %d unknown\n", (unsigned long long)S, k, j.src); return 1; }
         const int lo = j.span & 0xffff, hi = j.span >> 16;
         if (direct) {  // one level from W_idx, rows D_s of this length
           if (k != 0 || j.src != -1 || j.poly < dbase || j.poly >= dend) bad++;
@@ -93,7 +93,8 @@ int check(uint64_t S, int ki, int back, bool rt = false) {
 // Dump mode: the facts tests/mt_levels.py models, as the real builder has
 // them.  Queries on stdin, one per line:
 //   S <ki> <S>    mt_levels(S, ki) -> one "S" line, then one "L" line per level with jobs
-//   N <ncoef>     mt_sub_len, mt_subs, dn_mt19937_device_scratch_bytes(ncoef, 1) -> one "N" line
+//   N <ncoef>     mt_sub_len, mt_subs, mt_scratch_bytes(ncoef) (dn_mt19937_device_scratch_bytes) -> one "N" line
+//   F <idx> <ncoef>  mt_final_plan(idx, ncoef, mt_subs, mt_sub_len) -> one "F" line
 // Built with -DDN_TUNING the DN_MT_BACK / DN_MT_RT knobs apply as in the
 // tuning library.  A level line: its jumps n, parts P, waves W, workgroups,
 // the most jobs of one workgroup, the part rows [lo, hi) it writes, the cut
@@ -148,7 +149,14 @@ int dump() {
         if (!H.lv[k].jobs.empty()) dump_level(k, H.lv[k]);
     } else if (q == 'N') {
       printf("N ncoef=%llu ki=%d S=%llu scratch=%llu head=%llu\n", a, mt_sub_len(a), (unsigned long long)mt_subs(a),
-             (unsigned long long)dn_mt19937_device_scratch_bytes(a, 1), (unsigned long long)kHead);
+             (unsigned long long)mt_scratch_bytes(a), (unsigned long long)kHead);
+    } else if (q == 'F') {
+      if (scanf("%llu", &b) != 1 || a > static_cast<unsigned long long>(kMtN) || !b) return 2;
+      const int ki = mt_sub_len(b);
+      const uint64_t S = mt_subs(b);
+      const MtFinal f = mt_final_plan(static_cast<int32_t>(a), b, S, ki);
+      printf("F idx=%llu ncoef=%llu ki=%d S=%llu sig=%d fidx=%d pos=%llu tf=%llu fin_lo=%d next_lo=%d\n", a, b, ki,
+             (unsigned long long)S, f.sig, f.fidx, (unsigned long long)f.pos, (unsigned long long)f.tf, f.fin_lo, f.next_lo);
     } else {
       return 2;
     }
