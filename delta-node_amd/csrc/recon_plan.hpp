@@ -9,7 +9,9 @@
 // (segment, local tile, live lanes, output offsets) — shared by the kernel
 // (shamir_m521.hip, reconstruct_many_kernel) and by a host program that checks
 // it against a per-element map (tests/host/recon_plan_check.cpp): it is the
-// one place where a mistake reads or writes outside a block.  Plain C++: no
+// one place where a mistake reads or writes outside a block.  Below it, the
+// host's decision whether a reconstruct call takes the five-limb kernels
+// (recon_low_eligible; tools/recon_low_check.cpp runs it).  Plain C++: no
 // HIP header.
 #pragma once
 
@@ -66,5 +68,24 @@ DN_SEG_HD bool recon_live(uint64_t n_elem, uint32_t lt, uint32_t w) { return rec
 // ... and the tile starts at this byte of a share row or of the tiled output
 // (the int64 output's index is recon_elem itself).
 DN_SEG_HD uint64_t recon_tile_offset(uint32_t lt) { return static_cast<uint64_t>(lt) * kSegTileBytes; }
+
+// Whether a reconstruct call may take the five-limb path (recon_low.hpp): it
+// asks for the int64 words alone (no field output, no overflow counter: that
+// one needs every limb, and asking for it is how a caller keeps the full
+// validation), the weights are one limb wide with d = 1, and sum |a_i| < 2^24
+// (the bound behind recon_low_word's q).  a: the k weights' limbs, `stride`
+// u32 apart; *a_sum receives the sum when the call is eligible.  Decided once
+// per call on the host; the unrolled kernels cover k = 2..5 (recon_low_covers).
+constexpr uint64_t kReconLowMaxSum = 1ull << 24;
+DN_SEG_HD bool recon_low_eligible(bool want_u64, bool want_fe, bool want_overflow, int a_limbs, int has_inv, int k,
+                                  const uint32_t* a, uint32_t stride, uint32_t* a_sum) {
+  if (!want_u64 || want_fe || want_overflow || a_limbs != 1 || has_inv != 0 || k < 1) return false;
+  uint64_t sum = 0;
+  for (int i = 0; i < k; ++i) sum += a[static_cast<uint64_t>(i) * stride];
+  if (sum >= kReconLowMaxSum) return false;
+  *a_sum = static_cast<uint32_t>(sum);
+  return true;
+}
+DN_SEG_HD bool recon_low_covers(int k) { return k >= 2 && k <= 5; }
 
 }  // namespace dn

@@ -26,6 +26,7 @@
 #include "chacha_device.hpp"
 #include "dn_internal.hpp"
 #include "m521_device.hpp"
+#include "recon_low.hpp"
 #include "recon_plan.hpp"
 
 namespace dn {
@@ -511,7 +512,7 @@ struct ReconArgs {
   int32_t k;
   uint32_t neg;
   uint32_t shift;
-  int32_t pad;
+  uint32_t a_sum;  // sum |a_i| (the five-limb kernels only)
   uint32_t a[DN_MAX_RESOLVE][kLimbs];
   uint32_t inv[kLimbs];
   uint32_t d, d_inv32, p_inv_d, pad2;
@@ -770,6 +771,170 @@ __global__ void __launch_bounds__(kBlock) reconstruct_many_kernel(const ReconMan
   }
 }
 
+// ---- five-limb reconstruct (int64 output alone) ------------------------------
+// A call that asks for the low 64 bits and nothing else (recon_low_eligible,
+// recon_plan.hpp) needs limbs 0, 1, 2, 15 and hi of every share row: 18 of its
+// 66 bytes per element (recon_low.hpp has the arithmetic and why it is exact).
+// A wave takes a whole tile in one pass, lane l elements 4l .. 4l + 3: per
+// share row four 16-byte loads (one 1-KB plane row per wave-instruction, as
+// split_wide_kernel at E = 4) and one 8-byte load of the hi plane, all 5 K of
+// them issued before the first multiply; its four words leave as 32
+// contiguous bytes.  A partial last tile, and a wave that owns one quarter of
+// a tile (wave_sched mode 3), take one element per lane, guarded by n_elem.
+template <int K>
+struct LowRows {
+  u32x4_t p[K][4];  // plane rows 0, 1, 2, 15: elements 4 lane .. 4 lane + 3
+  u32x2_t hi[K];    // their four 16-bit tops
+};
+
+template <int K, typename Row>
+__device__ __forceinline__ void low_load(Row row, uint32_t tile, uint32_t lane, LowRows<K>& b) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const rsrc_t r = tile_rsrc(tile_base(row(i), tile));
+    b.p[i][0] = __builtin_amdgcn_raw_buffer_load_b128(r, 16u * lane, 0, kNt);
+    b.p[i][1] = __builtin_amdgcn_raw_buffer_load_b128(r, 16u * lane, 4 * kTile, kNt);
+    b.p[i][2] = __builtin_amdgcn_raw_buffer_load_b128(r, 16u * lane, 2 * 4 * kTile, kNt);
+    b.p[i][3] = __builtin_amdgcn_raw_buffer_load_b128(r, 16u * lane, kLowTopLimb * 4 * kTile, kNt);
+    b.hi[i] = __builtin_amdgcn_raw_buffer_load_b64(r, 8u * lane, static_cast<int>(kHiOffset), kNt);
+  }
+  // (without it the scheduler sinks the last loads below the first multiplies)
+  __builtin_amdgcn_sched_barrier(0);
+}
+
+// The four words of a loaded whole tile; out = the tile's first word.
+template <int K>
+__device__ __forceinline__ void low_emit(const ReconArgs& a, int64_t* out, uint32_t lane, const LowRows<K>& b) {
+  uint32_t aw[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) aw[i] = a.a[i][0];
+  uint64_t o[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    uint32_t y[K][kLowPlanes];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+#pragma unroll
+      for (int l = 0; l < 4; ++l) y[i][l] = b.p[i][l][e];
+      y[i][4] = b.hi[i][e / 2] >> (16 * (e % 2));
+    }
+    o[e] = recon_low_word<K>(y, aw, a.neg, a.shift, a.a_sum);
+  }
+  const rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(out, 0, kTile * 8, 0x00020000);
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    u32x4_t v;
+    v.x = static_cast<uint32_t>(o[2 * h]), v.y = static_cast<uint32_t>(o[2 * h] >> 32);
+    v.z = static_cast<uint32_t>(o[2 * h + 1]), v.w = static_cast<uint32_t>(o[2 * h + 1] >> 32);
+    __builtin_amdgcn_raw_buffer_store_b128(v, ro, 32u * lane + 16u * h, 0, kNt);
+  }
+}
+
+// Quarters [ws.q0, ws.q1) of a tile, one element per lane; no lane at or past
+// n_elem is read or written.
+template <int K, typename Row>
+__device__ __forceinline__ void low_tile_narrow(const ReconArgs& a, Row row, uint64_t n_elem, int64_t* out_u64,
+                                                uint32_t tile, const WaveSched& ws, uint32_t lane) {
+  uint32_t aw[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) aw[i] = a.a[i][0];
+#pragma unroll 1
+  for (uint32_t q = ws.q0; q < ws.q1; ++q) {
+    const uint32_t w = lane + 64u * q;
+    if (!recon_live(n_elem, tile, w)) break;
+    uint32_t y[K][kLowPlanes];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      const rsrc_t r = tile_rsrc(tile_base(row(i), tile));
+      y[i][0] = __builtin_amdgcn_raw_buffer_load_b32(r, 4u * w, 0, kNt);
+      y[i][1] = __builtin_amdgcn_raw_buffer_load_b32(r, 4u * w, 4 * kTile, kNt);
+      y[i][2] = __builtin_amdgcn_raw_buffer_load_b32(r, 4u * w, 2 * 4 * kTile, kNt);
+      y[i][3] = __builtin_amdgcn_raw_buffer_load_b32(r, 4u * w, kLowTopLimb * 4 * kTile, kNt);
+      y[i][4] = __builtin_amdgcn_raw_buffer_load_b16(r, 2u * w, static_cast<int>(kHiOffset), kNt);
+    }
+    const uint64_t o = recon_low_word<K>(y, aw, a.neg, a.shift, a.a_sum);
+    __builtin_nontemporal_store(static_cast<int64_t>(o), out_u64 + recon_elem(tile, w));
+  }
+}
+
+// One tile: whole and the wave's own, or by quarters.
+template <int K, typename Row>
+__device__ __forceinline__ void low_tile(const ReconArgs& a, Row row, uint64_t n_elem, int64_t* out_u64,
+                                         uint32_t tile, const WaveSched& ws, uint32_t lane) {
+  if (ws.q0 == 0u && ws.q1 == 4u && recon_tile_full(n_elem, tile)) {
+    LowRows<K> y;
+    low_load<K>(row, tile, lane, y);
+    low_emit<K>(a, out_u64 + recon_elem(tile, 0u), lane, y);
+  } else {
+    low_tile_narrow<K>(a, row, n_elem, out_u64, tile, ws, lane);
+  }
+}
+
+// DN_RECON_LOW_PF (default 0): a wave with several whole tiles loads tile
+// t + step's rows before tile t's arithmetic, alternating between two sets of
+// registers (36 K VGPRs instead of 18 K).  DESIGN.md §4.2 has the measurement.
+#ifndef DN_RECON_LOW_PF
+#define DN_RECON_LOW_PF 0
+#endif
+
+// reconstruct_kernel's five-limb form.
+template <int K>
+__global__ void __launch_bounds__(kBlock) reconstruct_low_kernel(const ReconArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const WaveSched ws = wave_sched(a.tile_map, a.ntiles);
+  const auto row = [&](int i) { return a.shares[i]; };
+  uint32_t tile = ws.first;
+#if DN_RECON_LOW_PF
+  if (ws.q0 == 0u && ws.q1 == 4u) {
+    // (only a vector's last tile can be partial: the whole ones come first)
+    const auto whole = [&](uint32_t t) { return t < ws.end && recon_tile_full(a.n_elem, t); };
+    LowRows<K> y0, y1;
+    bool more = whole(tile);
+    if (more) low_load<K>(row, tile, lane, y0);
+    while (more) {
+      uint32_t next = tile + ws.step;
+      more = whole(next);
+      if (more) low_load<K>(row, next, lane, y1);
+      low_emit<K>(a, a.out_u64 + recon_elem(tile, 0u), lane, y0);
+      tile = next;
+      if (!more) break;
+      next = tile + ws.step;
+      more = whole(next);
+      if (more) low_load<K>(row, next, lane, y0);
+      low_emit<K>(a, a.out_u64 + recon_elem(tile, 0u), lane, y1);
+      tile = next;
+    }
+  }
+#endif
+  for (; tile < ws.end; tile += ws.step) low_tile<K>(a, row, a.n_elem, a.out_u64, tile, ws, lane);
+}
+
+// reconstruct_many_kernel's five-limb form: the same walk over the global tile
+// range, the same tile bodies with the segment's rows, n_elem and output.
+template <int K>
+__global__ void __launch_bounds__(kBlock) reconstruct_many_low_kernel(const ReconManyArgs a) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const WaveSched ws = wave_sched(a.r.tile_map, a.r.ntiles);
+  if (ws.first >= ws.end) return;
+  const ReconTab tab = (ReconTab)a.segs;
+  const ReconRowTab rows = (ReconRowTab)a.rows;
+  uint32_t seg = __builtin_amdgcn_readfirstlane(recon_seg_find(tab, a.nseg, ws.first));
+  for (uint32_t tile = ws.first; tile < ws.end; tile += ws.step) {
+    seg = __builtin_amdgcn_readfirstlane(recon_seg_step(tab, seg, tile));
+    const uint32_t lt = tile - tab[seg].tile_begin;
+    const uint64_t n_elem = tab[seg].n_elem;
+    int64_t* const out = tab[seg].out_u64;
+    const ReconRowTab r0 = rows + static_cast<uint64_t>(seg) * K;
+    low_tile<K>(a.r, [&](int i) { return r0[i]; }, n_elem, out, lt, ws, lane);
+  }
+}
+
+// DN_RECON_LOW=0 keeps an eligible call on the full path (A/B hook, read per call).
+static bool recon_low_on() {
+  const char* e = tune_env("DN_RECON_LOW");
+  return !(e && e[0] == '0');
+}
+
 // DN_RECON_UNROLL=0 selects the runtime-k kernel (A/B hook, read per call).
 static bool recon_unroll() {
   const char* e = tune_env("DN_RECON_UNROLL");
@@ -806,6 +971,33 @@ static void launch_recon_many_k(int k, dim3 g, hipStream_t s, const ReconManyArg
     }
   }
   hipLaunchKernelGGL((reconstruct_many_kernel<A, INV, 0>), g, dim3(kBlock), 0, s, a);
+}
+
+// Whether this call takes the five-limb kernels, and a.a_sum if it does:
+// recon_low_eligible, a share count they are unrolled for, neither A/B hook set.
+static bool recon_low_route(ReconArgs& a, const dn_m521_lagrange_t* w, bool want_u64, bool want_fe,
+                            bool want_overflow) {
+  return recon_low_on() && recon_unroll() && recon_low_covers(w->k) &&
+         recon_low_eligible(want_u64, want_fe, want_overflow, w->a_limbs, w->has_inv, w->k, &w->a[0][0], kLimbs,
+                            &a.a_sum);
+}
+
+static void launch_recon_low(int k, dim3 g, hipStream_t s, const ReconArgs& a) {
+  switch (k) {
+    case 2: hipLaunchKernelGGL((reconstruct_low_kernel<2>), g, dim3(kBlock), 0, s, a); return;
+    case 3: hipLaunchKernelGGL((reconstruct_low_kernel<3>), g, dim3(kBlock), 0, s, a); return;
+    case 4: hipLaunchKernelGGL((reconstruct_low_kernel<4>), g, dim3(kBlock), 0, s, a); return;
+    default: hipLaunchKernelGGL((reconstruct_low_kernel<5>), g, dim3(kBlock), 0, s, a); return;
+  }
+}
+
+static void launch_recon_many_low(int k, dim3 g, hipStream_t s, const ReconManyArgs& a) {
+  switch (k) {
+    case 2: hipLaunchKernelGGL((reconstruct_many_low_kernel<2>), g, dim3(kBlock), 0, s, a); return;
+    case 3: hipLaunchKernelGGL((reconstruct_many_low_kernel<3>), g, dim3(kBlock), 0, s, a); return;
+    case 4: hipLaunchKernelGGL((reconstruct_many_low_kernel<4>), g, dim3(kBlock), 0, s, a); return;
+    default: hipLaunchKernelGGL((reconstruct_many_low_kernel<5>), g, dim3(kBlock), 0, s, a); return;
+  }
 }
 
 // Compute units of the current device (cached per device id).
@@ -1169,6 +1361,10 @@ extern "C" int dn_m521_reconstruct(const void* const* share_vecs, const dn_m521_
   hipStream_t s = static_cast<hipStream_t>(stream);
   rc = recon_set_weights(a, w, name);
   if (rc != DN_OK) return rc;
+  if (recon_low_route(a, w, out_u64 != nullptr, out_fe != nullptr, overflow_count != nullptr)) {
+    launch_recon_low(w->k, g, s, a);
+    return check_launch(name);
+  }
   DN_RECON_DISPATCH(launch_recon_k, w, w->k, g, s, a)
   return check_launch(name);
 }
@@ -1246,6 +1442,11 @@ extern "C" int dn_m521_reconstruct_many(const uint64_t* n_elem, const void* cons
   a.r.ntiles = ntiles;
   const dim3 g(grid_for(ntiles));
   a.r.tile_map = tile_map_for(static_cast<int>(g.x));
+  // (the counters are one pointer per call: asking for any keeps the full path)
+  if (recon_low_route(a.r, w, out_u64 != nullptr, out_fe != nullptr, overflow_counts != nullptr)) {
+    launch_recon_many_low(w->k, g, st, a);
+    return check_launch(name);
+  }
   DN_RECON_DISPATCH(launch_recon_many_k, w, w->k, g, st, a)
   return check_launch(name);
 }

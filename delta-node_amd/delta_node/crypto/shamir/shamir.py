@@ -479,6 +479,9 @@ class SecretShare(object):
         out     "int64": int64 tensor [n] holding the low 64 bits (the secret's
                 two's-complement view); "field": uint8 tiled vector [vec_bytes(n)]
         return_overflow  also return a uint32 device counter of elements >= 2^64
+                (and read every limb: without it the int64 words come from the
+                five limbs of each share they depend on, exact for every result
+                below 2^480 — dn_m521_reconstruct in include/dn_shamir.h)
         Same checks as `resolve_shares` (too few, duplicates, k == 1).
         """
         self._require_m521()

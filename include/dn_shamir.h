@@ -157,6 +157,16 @@ int dn_m521_lagrange(const uint64_t* xs, int k, int threshold, dn_m521_lagrange_
  *   out_u64       device int64[n_elem] (low 64 bits of the result), or NULL
  *   overflow_count device uint32 counter, incremented (atomically) once per
  *                 element whose result is >= 2^64; may be NULL
+ * With out_u64 alone (out_fe and overflow_count NULL) the words are exact for
+ * every result below 2^480 — every int64 secret and every sum of them: for
+ * one-limb weights with d = 1 and sum |a_i| < 2^24 the call then reads only
+ * the five limbs of each share those 64 bits depend on (limbs 0, 1, 2, 15 and
+ * the top 9 bits), and a result r with r * 2^shift mod p within
+ * (sum |a_i| + 2) * 2^480 of p may come out with another low word.  Rows
+ * that are no sharing of a small value can land there (a corrupted sharing of
+ * an int64 does, about every other time), so a caller that validates passes
+ * overflow_count: with a counter or a field output every limb is read and the
+ * result is the canonical residue's, always.
  * Replaces shamir.py:68-90.
  */
 int dn_m521_reconstruct(const void* const* share_vecs, const dn_m521_lagrange_t* w,
@@ -180,7 +190,10 @@ int dn_m521_reconstruct(const void* const* share_vecs, const dn_m521_lagrange_t*
  *                   untouched until the work queued on `stream` has run
  * A vector with n_elem[j] == 0 is skipped and none of its pointers is read.
  * At most 65536 vectors.  Validation and codes as dn_m521_reconstruct.  The
- * results equal dn_m521_reconstruct on vector 0, 1, ... in turn.
+ * results equal dn_m521_reconstruct on vector 0, 1, ... in turn: with out_u64
+ * alone (out_fe and overflow_counts NULL) the words are exact for every result
+ * below 2^480, as described there; with counters or field outputs every limb
+ * of every vector is read.
  *
  * Like dn_m521_reconstruct this call does NOT synchronise `stream`.  The
  * table (tile ranges, outputs, row addresses) is written into a pinned host
@@ -520,7 +533,10 @@ int dn_m521_encode_shares_many(const uint64_t* n_elem, const void* const* blocks
  * back to back with offsets[n_elem + 1]); element e of the result is
  *     sum_i lambda_i * (y of record e of wire i mod p)  mod p, canonical.
  * Outputs and *overflow_count are bit for bit those of dn_m521_decode_shares
- * on every wire followed by dn_m521_reconstruct, without the k intermediate
+ * on every wire followed by dn_m521_reconstruct with every limb read (its form
+ * with a counter or a field output: this call keeps the full arithmetic also
+ * when out_u64 alone is asked for, a packed record being parsed whole anyway;
+ * the two agree wherever the result is below 2^480), without the k intermediate
  * tiled vectors: each record is parsed as the decoder parses it (x up to 8
  * bytes, leading zero bytes of y allowed, y up to 68 significant bytes reduced
  * mod p, untrusted offsets) and interpolated in registers.
