@@ -61,6 +61,19 @@ class Lagrange(ctypes.Structure):
     ]
 
 
+class CheckPlan(ctypes.Structure):
+    """Mirror of dn_m521_check_plan_t."""
+
+    _fields_ = [
+        ("k", ctypes.c_int32),
+        ("r", ctypes.c_int32),
+        ("neg", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("c", (ctypes.c_uint64 * MAX_RESOLVE) * 4),
+        ("xp", (ctypes.c_uint32 * MAX_RESOLVE) * 4),
+    ]
+
+
 class Segment(ctypes.Structure):
     """Mirror of dn_m521_segment_t."""
 
@@ -114,6 +127,8 @@ _SYMBOLS = {
     "dn_m521_reconstruct_records": (i32, [pvp, pu64, pvp, pu64, ctypes.POINTER(Lagrange), vp, vp, vp, vp, u64, vp],
                                     False),
     "dn_m521_sum_records": (i32, [pvp, pu64, pvp, u64, u64, cp, vp, vp, vp, u64, vp], False),
+    "dn_m521_check_plan": (i32, [pu64, i32, i32, ctypes.POINTER(CheckPlan)], False),
+    "dn_m521_check_shares": (i32, [pvp, ctypes.POINTER(CheckPlan), vp, vp, u64, vp], False),
 }
 EXPORTS = tuple(_SYMBOLS)
 
@@ -405,6 +420,30 @@ def sum_records(wires: Sequence, x: int, negate: Optional[Sequence[bool]], bad, 
         raise ValueError("sum_records: x must fit 64 bits")
     check(L.dn_m521_sum_records(*_wire_arrays(wires), m, int(x), neg, _ptr(acc), _ptr(out), _ptr(bad), n,
                                 stream_ptr()))
+
+
+def check_plan(xs: Sequence[int], threshold: int) -> CheckPlan:
+    """The parity-check weights of abscissas xs for `threshold`
+    (dn_m521_check_plan; host only).  Raises as `lagrange` does, and
+    NotImplementedError for the check's own limits."""
+    L = need(lib(), "dn_m521_check_plan")
+    plan = CheckPlan()
+    arr = (ctypes.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
+    check(L.dn_m521_check_plan(arr, len(xs), threshold, ctypes.byref(plan)))
+    return plan
+
+
+def check_shares(share_vecs: Sequence, plan: CheckPlan, counts, culprit=None, n: int = 0) -> None:
+    """One consistency pass over plan.k share vectors (dn_m521_check_shares):
+    counts a device int32 / uint32 tensor [2] the kernel ADDS to (inconsistent
+    elements; those with a located culprit), culprit a device uint8 tensor [n]
+    or None.  Does not synchronise."""
+    L = need(lib(), "dn_m521_check_shares")
+    k = len(share_vecs)
+    if k != plan.k:
+        raise ValueError("check_shares: plan/share count mismatch")
+    ptrs = (ctypes.c_void_p * k)(*[v.data_ptr() for v in share_vecs])
+    check(L.dn_m521_check_shares(ptrs, ctypes.byref(plan), _ptr(counts), _ptr(culprit), n, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

@@ -503,6 +503,55 @@ class SecretShare(object):
         _resolve_vectors(vecs, xs, n, self.threshold, out_fe=out_fe, out_u64=out_u64, overflow=over)
         return (res, over) if return_overflow else res
 
+    def check_shares_vec(self, shares, xs: Sequence[int], n: int, *, culprit: bool = False, bad=None):
+        """Do the k > threshold share vectors lie, element by element, on one
+        polynomial of degree < threshold — and where they do not, which single
+        share is off?  `resolve_shares_vec` interpolates through every row it
+        is given (shamir.py:68-90): one bad row of five yields a wrong secret
+        and no signal.  This is the check to run before it; one launch, every
+        row read once (dn_m521_check_shares).
+
+        shares, xs, n  as `resolve_shares_vec`, with its abscissa checks,
+                 messages and exception types, all before any device use
+        culprit  also return a uint8 device tensor [n]: 0xFF for a consistent
+                 element, i (the index into xs) for the single share whose
+                 change alone makes the element consistent, 0xFE for an
+                 inconsistent element that no single share explains (always
+                 so with one spare share: k == threshold + 1 detects only)
+        bad      None: one read-back after the launch; returns the number of
+                 inconsistent elements as an int, or (count, culprit).  An
+                 int32 device tensor [2]: bad[0] += inconsistent elements,
+                 bad[1] += those with a located culprit (only with culprit),
+                 on the device; the call does not synchronise, can be captured
+                 into a graph, and returns None, or (None, culprit)
+        NotImplementedError for the device's limits, as for t <= 64: k ==
+        threshold (no spare share), more than 4 spare shares, more than 16
+        shares, an abscissa 0 or one past 64 bits, integer weights
+        |w_i| x_i^j of 2^32 or more.  There is no CPU fallback."""
+        self._require_m521()
+        import torch
+
+        what = "check_shares_vec"
+        vecs = _args.rows_of(shares)
+        xs = [int(x) for x in xs]
+        if len(vecs) != len(xs):
+            raise ValueError("check_shares_vec: one abscissa per share vector")
+        self._check_abscissas(xs)
+        if not all(_args.fits_u64(x) for x in xs):
+            raise NotImplementedError("check_shares_vec: abscissas must fit 64 bits")
+        plan = _native.check_plan(xs, self.threshold)
+        dev = _device()
+        vb = field.vec_bytes(n)
+        for v in vecs:
+            if v.dtype != torch.uint8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
+                raise ValueError(f"check_shares_vec: share vectors must be contiguous uint8 [{vb}] on {dev}")
+        _args.check_bad_flag(what, bad, dev, "share vectors")
+        bad, checked = _args.bad_flag(bad, dev)
+        marks = torch.empty(n, dtype=torch.uint8, device=dev) if culprit else None
+        _native.check_shares(vecs, plan, bad, marks, n)
+        count = int(bad[0].item()) if checked else None
+        return (count, marks) if culprit else count
+
     def resolve_records_vec(self, records, xs: Optional[Sequence[int]], n: int, *, out: str = "int64",
                             return_overflow: bool = False, bad=None):
         """Interpolate at 0 straight from wire records — `resolve_shares`

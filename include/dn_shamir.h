@@ -242,6 +242,65 @@ int dn_m521_sum_vecs(const void* const* vecs, const uint8_t* negate, uint64_t m,
                      void* stream);
 
 /*
+ * Share consistency check: do k > t shares of an element lie on ONE polynomial
+ * of degree < t, and if not, which single share is off?  The interpolation it
+ * guards (shamir.py:68-90, dn_m521_reconstruct) goes through all k rows it is
+ * given and returns a wrong secret without a signal when one of them is bad.
+ *
+ * For distinct abscissas let v_i = 1 / prod_{m != i} (x_i - x_m).  Every f of
+ * degree < t satisfies sum_i v_i x_i^j f(x_i) = 0 for j = 0 .. r - 1, r = k - t
+ * (the parity checks of the generalised Reed-Solomon code the shares form).
+ * Scaled by D = lcm_i |prod_{m != i} (x_i - x_m)| the weights are the signed
+ * integers w_i = D v_i (xs = 1..5: 1, -4, 6, -4, 1), and the syndromes are
+ *   S_j = sum_i w_i x_i^j y_i  (mod p),   j = 0 .. r - 1.
+ * The element is consistent iff every S_j == 0; for r >= 2 share i is the
+ * culprit (changing y_i alone makes the element consistent; at most one i
+ * does) iff S_0 != 0 and S_j == x_i^j S_0 for j = 1 .. r - 1.  No inversion.
+ *
+ * The plan holds the magnitudes c[j][i] = |w_i| x_i^j, the sign of w_i in bit
+ * i of `neg`, and the powers xp[j][i] = x_i^j of the culprit test.
+ */
+#define DN_M521_CHECK_MAX_R 4
+typedef struct dn_m521_check_plan {
+  int32_t k;    /* shares, t + 1 .. 16                         */
+  int32_t r;    /* k - threshold: syndromes, 1 .. 4            */
+  uint32_t neg; /* bit i set: w_i is negative                  */
+  uint32_t reserved;
+  uint64_t c[DN_M521_CHECK_MAX_R][DN_MAX_RESOLVE];  /* |w_i| x_i^j, each < 2^32 */
+  uint32_t xp[DN_M521_CHECK_MAX_R][DN_MAX_RESOLVE]; /* x_i^j                    */
+} dn_m521_check_plan_t;
+
+/* Host.  Validates as dn_m521_lagrange does, with its codes and messages (too
+ * few, duplicates, k == 1, k > DN_MAX_RESOLVE), then DN_ERR_UNSUPPORTED for:
+ * k == threshold (no spare share: nothing to check), r > 4, an abscissa 0, a
+ * product that leaves 128 bits, a c[j][i] >= 2^63, and a c[j][i] >= 2^32 — the
+ * kernel's bound: it multiplies a share limb by c in one 32 x 32 -> 64 bit
+ * step and keeps S_j unreduced in 18 limbs (k <= 16 such terms stay below
+ * 2^557).  threshold < 1 is DN_ERR_ARG. */
+int dn_m521_check_plan(const uint64_t* xs, int k, int threshold, dn_m521_check_plan_t* out);
+
+/*
+ * Device.  One pass over the k rows: every row is read once, the r syndromes
+ * of an element stay in registers, one byte per element is written.
+ *   share_vecs  HOST array of plan->k DEVICE pointers, tiled vectors of n_elem
+ *               canonical residues (as for dn_m521_reconstruct), in the order
+ *               of the plan's abscissas
+ *   counts      DEVICE uint32[2], ADDED to: [0] inconsistent elements, [1]
+ *               (only with `culprit`) those of them with a located culprit
+ *   culprit     DEVICE uint8[n_elem] or NULL.  Byte e: 0xFF consistent, i (the
+ *               index into xs) the single share that explains the element,
+ *               0xFE inconsistent and not explained by one share (always so
+ *               when r == 1)
+ * Lanes at or past n_elem in the last tile are neither read nor written.
+ * n_elem == 0 returns DN_OK and touches no pointer.  DN_ERR_ARG, before any
+ * device call: a null pointer (plan, share_vecs, a row, counts), a malformed
+ * plan, more than 2^32 tiles.  Does not synchronise `stream`; can be captured
+ * into a graph.
+ */
+int dn_m521_check_shares(const void* const* share_vecs, const dn_m521_check_plan_t* plan, uint32_t* counts,
+                         uint8_t* culprit, uint64_t n_elem, void* stream);
+
+/*
  * Host.  Draw the reference's coefficients with CPython's MT19937 semantics:
  * for each element e (in order) and j = 1..t-1, c = randint(1, p-1) =
  * 1 + getrandbits(521) rejected while >= p-1 (17 MT words, little-endian, last
