@@ -129,6 +129,7 @@ _SYMBOLS = {
     "dn_m521_sum_records": (i32, [pvp, pu64, pvp, u64, u64, cp, vp, vp, vp, u64, vp], False),
     "dn_m521_check_plan": (i32, [pu64, i32, i32, ctypes.POINTER(CheckPlan)], False),
     "dn_m521_check_shares": (i32, [pvp, ctypes.POINTER(CheckPlan), vp, vp, u64, vp], False),
+    "dn_m521_check_records": (i32, [pvp, pu64, pvp, pu64, ctypes.POINTER(CheckPlan), vp, vp, vp, u64, vp], False),
 }
 EXPORTS = tuple(_SYMBOLS)
 
@@ -444,6 +445,21 @@ def check_shares(share_vecs: Sequence, plan: CheckPlan, counts, culprit=None, n:
         raise ValueError("check_shares: plan/share count mismatch")
     ptrs = (ctypes.c_void_p * k)(*[v.data_ptr() for v in share_vecs])
     check(L.dn_m521_check_shares(ptrs, ctypes.byref(plan), _ptr(counts), _ptr(culprit), n, stream_ptr()))
+
+
+def check_records(wires: Sequence, xs: Sequence[int], plan: CheckPlan, counts, bad, culprit=None, n: int = 0) -> None:
+    """One consistency pass straight over plan.k wires (dn_m521_check_records):
+    wires[i] = (address of the packed records, their byte count, address of
+    uint64 / int64 offsets[n + 1]) of abscissa xs[i], plan that of
+    `check_plan(xs, t)`.  counts and culprit as `check_shares`, bad as
+    `reconstruct_records`: device int32 / uint32 tensors [2] the kernel ADDS
+    to.  Does not synchronise."""
+    L = need(lib(), "dn_m521_check_records")
+    k = len(wires)
+    if k != plan.k or k != len(xs):
+        raise ValueError("check_records: one wire and one abscissa per share of the plan")
+    check(L.dn_m521_check_records(*_wire_arrays(wires), (ctypes.c_uint64 * max(k, 1))(*[int(x) for x in xs]),
+                                  ctypes.byref(plan), _ptr(counts), _ptr(culprit), _ptr(bad), n, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

@@ -638,6 +638,89 @@ class SecretShare(object):
             codec.check_bad_records(bad)
         return (res, over) if return_overflow else res
 
+    def check_records_vec(self, records, xs: Optional[Sequence[int]], n: int, *, culprit: bool = False, bad=None,
+                          bad_records=None):
+        """`check_shares_vec` straight from wire records: do the k > threshold
+        wires lie, element by element, on one polynomial of degree < threshold
+        — and where they do not, which wire is off?  The check a receiver runs
+        before it trusts `resolve_records_vec`, on what that call reads: one
+        launch, no decoded vectors (dn_m521_check_records).
+
+        records, xs, n  as `resolve_records_vec` (xs=None takes each wire's x
+                 from its first record: the one form that synchronises before
+                 the launch), with its wire, abscissa and device checks,
+                 messages and exception types, all before any device use.  A
+                 `packed` view that is not 4-byte aligned is copied once
+        culprit, bad  as `check_shares_vec`: bad None is one read-back and the
+                 count (or (count, marks)) is returned; an int32 device tensor
+                 [2] is ADDED to on the device (inconsistent elements, those
+                 with a located culprit) and None (or (None, marks)) returned
+        bad_records  as `resolve_records_vec`'s bad: None is one read-back, and
+                 ValueError naming both counts when a record cannot be
+                 represented or carries an x other than its wire's; an int32
+                 device tensor [2] is ADDED to and
+                 `codec.check_bad_records(bad_records, "check_records_vec")`
+                 raises later
+        The call synchronises only where bad or bad_records is None; with both
+        given (and xs given) it can be captured into a graph.
+
+        The counts and every culprit byte are those of decode_share_vec on
+        every wire followed by check_shares_vec (an unrepresentable record
+        counts as y = 0 there and here, so its element is flagged with that
+        wire as the culprit unless 0 fits the others; a wrong-x record's y is
+        used).  The two record counts are those of resolve_records_vec on the
+        same wires.
+
+        NotImplementedError for check_shares_vec's limits — k == threshold,
+        more than 4 spare shares, more than 16 wires, an abscissa 0 or one past
+        64 bits, integer weights of 2^32 or more — with no decode fallback.
+        There is no CPU fallback."""
+        self._require_m521()
+        import torch
+
+        from . import codec
+
+        what = "check_records_vec"
+        recs = _args.wire_pairs(what, records)
+
+        def plan_of(xs):
+            self._check_abscissas(xs)
+            if not all(_args.fits_u64(x) for x in xs):
+                raise NotImplementedError("check_records_vec: abscissas must fit 64 bits")
+            return _native.check_plan(xs, self.threshold)
+
+        plan = None
+        if xs is not None:
+            xs = [int(x) for x in xs]
+            if len(recs) != len(xs):
+                raise ValueError("check_records_vec: one abscissa per wire")
+            plan = plan_of(xs)
+        elif not recs:
+            raise ValueError("not enough values to unpack (expected 2, got 0)")
+        n = int(n)
+        if n < 0:
+            raise ValueError("check_records_vec: n must not be negative")
+        first = _args.check_wires(what, recs, n)
+        _args.check_bad_flag(what, bad, first, "records")
+        _args.check_bad_flag(what + ": bad_records", bad_records, first, "records")
+        if xs is None and n == 0:
+            raise ValueError("check_records_vec: xs=None needs a first record to read each abscissa from")
+        dev = _device()
+        if first != dev:
+            raise ValueError(f"check_records_vec: records must be on {dev}")
+        if xs is None:
+            xs = _first_record_xs(recs, what)
+            plan = plan_of(xs)
+        bad, checked = _args.bad_flag(bad, dev)
+        bad_records, records_checked = _args.bad_flag(bad_records, dev)
+        marks = torch.empty(n, dtype=torch.uint8, device=dev) if culprit else None
+        recs, wires = _args.aligned_wires(recs)
+        _native.check_records(wires, xs, plan, bad, bad_records, marks, n)
+        if records_checked:
+            codec.check_bad_records(bad_records, what)
+        count = int(bad[0].item()) if checked else None
+        return (count, marks) if culprit else count
+
     def _check_abscissas(self, xs: Sequence[int]) -> None:
         """resolve_shares' checks on the abscissas (shamir.py:70-83), with its messages."""
         if len(xs) == 0:

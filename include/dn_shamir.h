@@ -628,6 +628,47 @@ int dn_m521_reconstruct_records(const uint8_t* const* in, const uint64_t* in_byt
                                 uint64_t n_elem, void* stream);
 
 /*
+ * The share consistency check straight from wire records: what a receiver
+ * runs before it trusts dn_m521_reconstruct_records (which, like shamir.py:68-90,
+ * interpolates through whatever it is given), on the wires that call reads and
+ * in one launch.  `counts` and every `culprit` byte are those of
+ * dn_m521_decode_shares on every wire followed by dn_m521_check_shares, without
+ * the k intermediate tiled vectors; `bad_counts` are those of
+ * dn_m521_reconstruct_records on the same wires.  Each record is parsed as the
+ * decoder parses it (x up to 8 bytes, leading zero bytes of y allowed, y up to
+ * 68 significant bytes reduced mod p, untrusted offsets) and its y enters the
+ * r syndromes in registers.
+ *   in, in_bytes, offsets, xs  HOST arrays of plan->k entries, as for
+ *                 dn_m521_reconstruct_records (in[i] DEVICE, 4-byte aligned, a
+ *                 16-byte aligned wire takes the wide path, wire by wire;
+ *                 offsets[i] DEVICE uint64[n_elem + 1], 8-byte aligned; xs[i]
+ *                 the abscissa wire i's records should carry), in the order of
+ *                 the plan's abscissas
+ *   plan          dn_m521_check_plan's for xs
+ *   counts        DEVICE uint32[2], ADDED to: [0] inconsistent elements, [1]
+ *                 (only with `culprit`) those of them with a located culprit
+ *   culprit       DEVICE uint8[n_elem] or NULL, as for dn_m521_check_shares
+ *   bad_counts    DEVICE uint32[2], ADDED to: [0] records the decoder cannot
+ *                 represent (such a record contributes y = 0, as its decoded
+ *                 vector would: its element is then flagged unless 0 fits the
+ *                 other shares), [1] representable records whose x is not
+ *                 xs[i] (their y is used all the same)
+ * Nothing outside in[i][0, in_bytes[i]) and offsets[i][0, n_elem] is read, and
+ * nothing is read or written for elements at or past n_elem.  n_elem == 0
+ * returns DN_OK and touches no pointer.  DN_ERR_ARG, before any device call: a
+ * null pointer, a malformed plan, a wire that is not 4-byte aligned, offsets
+ * that are not 8-byte aligned, 2^31 workgroups (of 256 elements) or more.  The
+ * wire descriptors and the plan travel in the kernel arguments: no device
+ * table, no staging buffer.  Does not synchronise `stream`; can be captured
+ * into a graph.  (No reference counterpart: shamir.py never checks its shares.)
+ */
+int dn_m521_check_records(const uint8_t* const* in, const uint64_t* in_bytes,
+                          const uint64_t* const* offsets, const uint64_t* xs,
+                          const dn_m521_check_plan_t* plan, uint32_t* counts /*[2]*/,
+                          uint8_t* culprit /*[n_elem] or NULL*/, uint32_t* bad_counts /*[2]*/,
+                          uint64_t n_elem, void* stream);
+
+/*
  * Sum of share wires: the party-side step of share-domain aggregation taken
  * straight from the records.  Party x holds share x of every member's tensor
  * as m wires (dn_m521_encode_shares' output: records [len(xb)][xb][yb] back to
