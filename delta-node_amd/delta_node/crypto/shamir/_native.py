@@ -74,6 +74,32 @@ class CheckPlan(ctypes.Structure):
     ]
 
 
+class DivSmall(ctypes.Structure):
+    """Mirror of dn_m521_div_small_t."""
+
+    _fields_ = [
+        ("d", ctypes.c_uint32),
+        ("shift", ctypes.c_uint32),
+        ("d_inv32", ctypes.c_uint32),
+        ("p_inv_d", ctypes.c_uint32),
+        ("d_recip", ctypes.c_uint64),
+        ("w", ctypes.c_uint32 * 17),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class RobustPlan(ctypes.Structure):
+    """Mirror of dn_m521_robust_plan_t."""
+
+    _fields_ = [
+        ("check", CheckPlan),
+        ("a", ctypes.c_uint32 * MAX_RESOLVE),
+        ("negate", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+        ("div", DivSmall * (MAX_RESOLVE + 1)),
+    ]
+
+
 class Segment(ctypes.Structure):
     """Mirror of dn_m521_segment_t."""
 
@@ -130,6 +156,8 @@ _SYMBOLS = {
     "dn_m521_check_plan": (i32, [pu64, i32, i32, ctypes.POINTER(CheckPlan)], False),
     "dn_m521_check_shares": (i32, [pvp, ctypes.POINTER(CheckPlan), vp, vp, u64, vp], False),
     "dn_m521_check_records": (i32, [pvp, pu64, pvp, pu64, ctypes.POINTER(CheckPlan), vp, vp, vp, u64, vp], False),
+    "dn_m521_robust_plan": (i32, [pu64, i32, i32, ctypes.POINTER(RobustPlan)], False),
+    "dn_m521_reconstruct_robust": (i32, [pvp, ctypes.POINTER(RobustPlan), vp, vp, vp, vp, u64, vp], False),
 }
 EXPORTS = tuple(_SYMBOLS)
 
@@ -460,6 +488,33 @@ def check_records(wires: Sequence, xs: Sequence[int], plan: CheckPlan, counts, b
         raise ValueError("check_records: one wire and one abscissa per share of the plan")
     check(L.dn_m521_check_records(*_wire_arrays(wires), (ctypes.c_uint64 * max(k, 1))(*[int(x) for x in xs]),
                                   ctypes.byref(plan), _ptr(counts), _ptr(culprit), _ptr(bad), n, stream_ptr()))
+
+
+def robust_plan(xs: Sequence[int], threshold: int) -> RobustPlan:
+    """`check_plan` with the all-k Lagrange integers and the division
+    constants of a robust reconstruct (dn_m521_robust_plan; host only).
+    Raises as `check_plan` does, and NotImplementedError for one spare share
+    and for the plan's own bounds."""
+    L = need(lib(), "dn_m521_robust_plan")
+    plan = RobustPlan()
+    arr = (ctypes.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
+    check(L.dn_m521_robust_plan(arr, len(xs), threshold, ctypes.byref(plan)))
+    return plan
+
+
+def reconstruct_robust(share_vecs: Sequence, plan: RobustPlan, counts, out_fe=None, out_u64=None, culprit=None,
+                       n: int = 0) -> None:
+    """Reconstruct past one bad share per element in one pass over
+    plan.check.k share vectors (dn_m521_reconstruct_robust): exactly one of
+    out_fe / out_u64 as `reconstruct`, counts and culprit as `check_shares`.
+    Does not synchronise."""
+    L = need(lib(), "dn_m521_reconstruct_robust")
+    k = len(share_vecs)
+    if k != plan.check.k:
+        raise ValueError("reconstruct_robust: plan/share count mismatch")
+    ptrs = (ctypes.c_void_p * k)(*[v.data_ptr() for v in share_vecs])
+    check(L.dn_m521_reconstruct_robust(ptrs, ctypes.byref(plan), _ptr(out_fe), _ptr(out_u64), _ptr(counts),
+                                       _ptr(culprit), n, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

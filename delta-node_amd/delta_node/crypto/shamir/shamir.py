@@ -552,6 +552,63 @@ class SecretShare(object):
         count = int(bad[0].item()) if checked else None
         return (count, marks) if culprit else count
 
+    def resolve_shares_vec_robust(self, shares, xs: Sequence[int], n: int, *, out: str = "int64",
+                                  culprit: bool = False, bad=None):
+        """`resolve_shares_vec` over k >= threshold + 2 share vectors that
+        survives ONE bad share per element: the check of `check_shares_vec`
+        and the reconstruction in one launch, every row read once
+        (dn_m521_reconstruct_robust).  Per element, by the culprit byte
+        `check_shares_vec(culprit=True)` gives it:
+
+        0xFF  consistent: the secret, `resolve_shares_vec` over all k rows;
+        i     share i located: the interpolant of the k - 1 other shares, what
+              `resolve_shares_vec` gives over any threshold of them;
+        0xFE  inconsistent and not explained by one share: the interpolant
+              through all k rows, as `resolve_shares_vec` (and shamir.py:68-90)
+              gives it — counted, so the caller knows not to trust it.
+
+        shares, xs, n  as `check_shares_vec`, with its checks, messages and
+                 exception types, all before any device use
+        out      "int64" | "field" as `resolve_shares_vec`; the int64 words are
+                 the low 64 bits of the canonical residue (every limb is read)
+        culprit  also return the uint8 device tensor [n] of culprit bytes
+        bad      None: one read-back after the launch; the count returned is
+                 the pair of ints (inconsistent, corrected): their difference
+                 is the number of elements not to trust (the 0xFE ones).  An
+                 int32 device tensor [2]: bad[0] += inconsistent
+                 elements, bad[1] += corrected ones, on the device; the call
+                 does not synchronise, can be captured into a graph, and the
+                 count returned is None
+        Returns (result, count) or (result, count, culprit).
+        NotImplementedError for `check_shares_vec`'s limits, for one spare
+        share (k == threshold + 1 detects only) and where a Lagrange integer
+        reaches 2^32 or a divisor's odd part 2^16.  There is no CPU fallback."""
+        self._require_m521()
+        import torch
+
+        what = "resolve_shares_vec_robust"
+        vecs = _args.rows_of(shares)
+        xs = [int(x) for x in xs]
+        if len(vecs) != len(xs):
+            raise ValueError(f"{what}: one abscissa per share vector")
+        self._check_abscissas(xs)
+        if not all(_args.fits_u64(x) for x in xs):
+            raise NotImplementedError(f"{what}: abscissas must fit 64 bits")
+        plan = _native.robust_plan(xs, self.threshold)
+        _args.check_out_form(what, out)
+        dev = _device()
+        vb = field.vec_bytes(n)
+        for v in vecs:
+            if v.dtype != torch.uint8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
+                raise ValueError(f"{what}: share vectors must be contiguous uint8 [{vb}] on {dev}")
+        _args.check_bad_flag(what, bad, dev, "share vectors")
+        bad, checked = _args.bad_flag(bad, dev)
+        marks = torch.empty(n, dtype=torch.uint8, device=dev) if culprit else None
+        res, out_fe, out_u64 = _args.result(out, n, vb, dev)
+        _native.reconstruct_robust(vecs, plan, bad, out_fe, out_u64, marks, n)
+        count = tuple(bad.tolist()) if checked else None
+        return (res, count, marks) if culprit else (res, count)
+
     def resolve_records_vec(self, records, xs: Optional[Sequence[int]], n: int, *, out: str = "int64",
                             return_overflow: bool = False, bad=None):
         """Interpolate at 0 straight from wire records — `resolve_shares`

@@ -669,6 +669,72 @@ int dn_m521_check_records(const uint8_t* const* in, const uint64_t* in_bytes,
                           uint64_t n_elem, void* stream);
 
 /*
+ * Robust reconstruct: f(0) per element from k >= t + 2 shares, past ONE bad
+ * share per element, in one pass — the decoding half of the check above.  The
+ * verdict v of an element is the culprit byte of dn_m521_check_shares, and
+ *   v == 0xFF  the output is f(0): dn_m521_reconstruct over all k rows;
+ *   v == i     the output is the interpolant at 0 of the k - 1 shares without
+ *              i: dn_m521_reconstruct over any t of them;
+ *   v == 0xFE  the output is the degree-(k-1) interpolant through all k rows,
+ *              what dn_m521_reconstruct gives; the element is counted.
+ * Next to the syndromes S_j the pass accumulates T = sum_m A_m y_m, where
+ * lambda_m = A_m / D_all are the Lagrange weights at 0 of all k abscissas in
+ * lowest terms (D_all the least common denominator).  A single error e_i in
+ * share i gives S_0 = w_i e_i and T = D_all f(0) + A_i e_i, hence
+ *   f(0) = (w_i T - A_i S_0) / (w_i D_all)   (mod p)
+ * and, with none, f(0) = T / D_all.  A divisor is d 2^shift with d odd: an
+ * exact division by d < 2^16 (as dn_m521_lagrange's has_inv == 2, same
+ * constants) and a rotation of the 521-bit string.  No inversion.
+ * (No reference counterpart: shamir.py:68-90 interpolates through every row.)
+ */
+typedef struct dn_m521_div_small {
+  uint32_t d;       /* odd part of the divisor, 1 <= d < 2^16              */
+  uint32_t shift;   /* its power of two                                    */
+  uint32_t d_inv32; /* d > 1: d^{-1} mod 2^32                              */
+  uint32_t p_inv_d; /* d > 1: p^{-1} mod d                                 */
+  uint64_t d_recip; /* d > 1: floor((2^64-1)/d)                            */
+  uint32_t w[DN_M521_LIMBS]; /* d > 1: 2^(32 l) mod d                      */
+  uint32_t reserved;
+} dn_m521_div_small_t;
+
+typedef struct dn_m521_robust_plan {
+  dn_m521_check_plan_t check;   /* the syndromes' weights: |w_i| is check.c[0][i] */
+  uint32_t a[DN_MAX_RESOLVE];   /* |A_m|, each < 2^32; A_m has the sign of w_m,
+                                   times -1 when k is even                  */
+  uint32_t negate;              /* 1 when k is even: the quotient is negated */
+  uint32_t reserved;
+  dn_m521_div_small_t div[DN_MAX_RESOLVE + 1]; /* [i]: |w_i| D_all; [DN_MAX_RESOLVE]: D_all */
+} dn_m521_robust_plan_t;
+
+/* Host.  Validates exactly as dn_m521_check_plan does (codes, messages, order)
+ * and fills out->check with its plan; then DN_ERR_UNSUPPORTED for: one spare
+ * share (r == 1: nothing can be attributed), a Lagrange product that leaves 128
+ * bits, an |A_m| >= 2^32 (the same one-limb bound as the syndromes' weights),
+ * and a divisor |w_i| D_all or D_all whose odd part is 2^16 or more. */
+int dn_m521_robust_plan(const uint64_t* xs, int k, int threshold, dn_m521_robust_plan_t* out);
+
+/*
+ * Device.  One launch, every row read once.
+ *   share_vecs  HOST array of plan->check.k DEVICE pointers, as for
+ *               dn_m521_check_shares
+ *   out_fe      DEVICE tiled vector of n_elem elements (canonical residues), or
+ *   out_u64     DEVICE int64[n_elem]: the low 64 bits of the canonical residue
+ *               (every limb of every share is read); exactly one of the two
+ *   counts      DEVICE uint32[2], ADDED to: [0] inconsistent elements, [1] those
+ *               of them with a located culprit — the corrected ones
+ *   culprit     DEVICE uint8[n_elem] or NULL: byte e is the verdict
+ * Lanes at or past n_elem in the last tile are neither read nor written.
+ * n_elem == 0 returns DN_OK and touches no pointer.  DN_ERR_ARG, before any
+ * device call: a null pointer (plan, share_vecs, a row, counts), both or neither
+ * of the outputs, a malformed plan, more than 2^32 tiles.  Weights, powers and
+ * every divisor's constants travel in the kernel arguments: no device table, no
+ * staging buffer.  Does not synchronise `stream`; can be captured into a graph.
+ */
+int dn_m521_reconstruct_robust(const void* const* share_vecs, const dn_m521_robust_plan_t* plan, void* out_fe,
+                               int64_t* out_u64, uint32_t* counts /*[2]*/, uint8_t* culprit /*[n_elem] or NULL*/,
+                               uint64_t n_elem, void* stream);
+
+/*
  * Sum of share wires: the party-side step of share-domain aggregation taken
  * straight from the records.  Party x holds share x of every member's tensor
  * as m wires (dn_m521_encode_shares' output: records [len(xb)][xb][yb] back to
