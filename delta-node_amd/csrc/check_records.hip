@@ -32,10 +32,9 @@
 // count: eight instantiations (R x culprit or not), none per k.
 #include <hip/hip_runtime.h>
 
-#include "check_core.hpp"
 #include "check_plan.hpp"
 #include "dn_internal.hpp"
-#include "m521_device.hpp"
+#include "share_rows.hpp"
 #include "wire_parse.hpp"
 
 namespace dn {
@@ -45,23 +44,13 @@ constexpr int kBlock = 256;
 static_assert(kBlock == kTile, "one workgroup per 256 elements");
 static_assert(kChkLimbs == kLimbs, "a parsed y is a syndrome term");
 
-struct Wire {
-  const uint8_t* in;        // packed records
-  uint64_t in_bytes;
-  const uint64_t* offsets;  // uint64[n_elem + 1]
-  uint64_t x;               // the abscissa every record should carry
-};
-
 struct Args {
   Wire wire[DN_MAX_RESOLVE];
-  uint32_t c[DN_M521_CHECK_MAX_R][DN_MAX_RESOLVE];   // |w_i| x_i^j
-  uint32_t xp[DN_M521_CHECK_MAX_R][DN_MAX_RESOLVE];  // x_i^j
+  CheckWeights wt;
   uint32_t* counts;  // [0] inconsistent elements, [1] those with a located culprit
   uint8_t* culprit;
   uint32_t* bad;     // [0] unrepresentable records, [1] records whose x is not the wire's
   uint64_t n_elem;
-  uint32_t k;
-  uint32_t neg;
   uint32_t w16;  // bit i: wire i is 16-B aligned (the wide staging path)
 };
 static_assert(sizeof(Args) <= 4096, "the kernel arguments must fit the 4 KB kernarg segment");
@@ -89,9 +78,8 @@ __device__ __forceinline__ void wire_step(const Args& a, uint32_t i, const uint3
       for (int l = 0; l < kLimbs; ++l) v[l] = 0u;
     }
     uint32_t c[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) c[j] = a.c[j][i];
-    check_mac<R>(S, v, c, 0u - ((a.neg >> i) & 1u));
+    const uint32_t sign = syndrome_weights<R>(a.wt, i, c);
+    check_mac<R>(S, v, c, sign);
   }
   nbad += static_cast<uint32_t>(__popcll(__ballot(valid && !ok)));
   nmis += static_cast<uint32_t>(__popcll(__ballot(valid && ok && x != a.wire[i].x)));
@@ -120,7 +108,7 @@ __global__ void __launch_bounds__(kBlock) check_records_kernel(const Args a) {
   const bool valid = e < a.n_elem;  // a dead lane reads and writes nothing
   const uint64_t eN = e0 + 64 < a.n_elem ? e0 + 64 : a.n_elem;
   uint32_t* W = s_win[wv] + kWinPad / 4;  // W[j] = dword at window byte 4j
-  const uint32_t k = a.k;                 // >= 2
+  const uint32_t k = a.wt.k;              // >= 2
 
   uint32_t S[R][kChkAcc];
 #pragma unroll
@@ -147,18 +135,14 @@ __global__ void __launch_bounds__(kBlock) check_records_kernel(const Args a) {
   uint8_t verdict = kChkConsistent;
   if (valid) {
     if constexpr (CULPRIT) {
-      verdict = check_verdict<R>(S, static_cast<int>(k), [&a](int j, int s) { return a.xp[j][s]; });
+      verdict = check_verdict<R>(S, static_cast<int>(k), [&a](int j, int s) { return a.wt.xp[j][s]; });
       a.culprit[e] = verdict;
     } else {
       verdict = check_consistent<R>(S) ? kChkConsistent : kChkUnexplained;
     }
   }
-  // one atomic per wave and counter, only where non-zero
-  const uint64_t off = __ballot(verdict != kChkConsistent);
-  const uint64_t found = CULPRIT ? __ballot(verdict < kChkUnexplained) : 0ull;
-  if (lane == 0u) {
-    if (off) atomicAdd(a.counts, static_cast<uint32_t>(__popcll(off)));
-    if (found) atomicAdd(a.counts + 1, static_cast<uint32_t>(__popcll(found)));
+  verdict_count<CULPRIT>(a.counts, verdict);
+  if (lane == 0) {
     if (nbad) atomicAdd(a.bad, nbad);
     if (nmis) atomicAdd(a.bad + 1, nmis);
   }
@@ -192,37 +176,15 @@ extern "C" int dn_m521_check_records(const uint8_t* const* in, const uint64_t* i
   if (blocks >= (1ull << 31)) return set_error(DN_ERR_ARG, "%s: n_elem %llu needs 2^31 workgroups or more", name,
                                                (unsigned long long)n_elem);
   cr::Args a{};
-  for (int i = 0; i < plan->k; ++i) {
-    if (!in[i] || !offsets[i]) return set_error(DN_ERR_ARG, "%s: null wire %d", name, i);
-    // the narrow path loads dwords from in + (an offset that is a multiple of 4)
-    if (reinterpret_cast<uintptr_t>(in[i]) & 3u)
-      return set_error(DN_ERR_ARG, "%s: wire %d must be 4-byte aligned", name, i);
-    if (reinterpret_cast<uintptr_t>(offsets[i]) & 7u)
-      return set_error(DN_ERR_ARG, "%s: offsets of wire %d must be 8-byte aligned", name, i);
-    a.wire[i].in = in[i];
-    a.wire[i].in_bytes = in_bytes[i];
-    a.wire[i].offsets = offsets[i];
-    a.wire[i].x = xs[i];
-    if ((reinterpret_cast<uintptr_t>(in[i]) & 15u) == 0) a.w16 |= 1u << i;
-    for (int j = 0; j < plan->r; ++j) {
-      a.c[j][i] = static_cast<uint32_t>(plan->c[j][i]);
-      a.xp[j][i] = plan->xp[j][i];
-    }
-  }
-#ifdef DN_TUNING
-  if (tune_env("DN_DECODE_W4") && tune_env("DN_DECODE_W4")[0] == '1') a.w16 = 0u;  // A/B: 4-B staging
-#endif
+  if (const int rc = fill_wires(name, in, in_bytes, offsets, xs, plan->k, a.wire, &a.w16)) return rc;
+  weights_fill(a.wt, *plan);
   a.counts = counts;
   a.culprit = culprit;
   a.bad = bad_counts;
   a.n_elem = n_elem;
-  a.k = static_cast<uint32_t>(plan->k);
-  a.neg = plan->neg;
   const dim3 g(static_cast<uint32_t>(blocks));
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (culprit) cr::launch<true>(plan->r, g, s, a);
   else cr::launch<false>(plan->r, g, s, a);
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return set_error(DN_ERR_HIP, "%s: launch failed: %s", name, hipGetErrorString(err));
-  return DN_OK;
+  return launch_status(name);
 }

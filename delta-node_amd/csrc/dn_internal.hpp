@@ -28,6 +28,43 @@ inline const char* tune_env(const char* name) {
 // Record a thread-local error message and return `code` (printf-style).
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// The most workgroups of a launch whose workgroups stride over their work:
+// 16384 (2^24 elements: one tile per wave; 1-3 % ahead of 4096 on reconstruct,
+// profiles/r01/tune_gridcap*.jsonl), or the tuning build's DN_GRID_CAP.
+inline uint64_t grid_cap(uint64_t otherwise = 16384u) {
+  const char* s = tune_env("DN_GRID_CAP");
+  const int v = s ? std::atoi(s) : 0;
+  return v > 0 ? static_cast<uint64_t>(v) : otherwise;
+}
+
+// The end of an entry point: DN_OK, or the launch's error recorded under
+// `name` (shamir_m521.hip).
+int launch_status(const char* name);
+
+// The k wires of a records entry point into its kernel arguments (Wire of
+// wire_parse.hpp): none null, `in` 4-byte and `offsets` 8-byte aligned; bit i
+// of *w16 says that wire i is 16-byte aligned (none where the tuning build's
+// DN_DECODE_W4 is 1: A/B of the 4-byte staging).
+template <typename W>
+int fill_wires(const char* name, const uint8_t* const* in, const uint64_t* in_bytes, const uint64_t* const* offsets,
+               const uint64_t* xs, int k, W* wire, uint32_t* w16) {
+  for (int i = 0; i < k; ++i) {
+    if (!in[i] || !offsets[i]) return set_error(DN_ERR_ARG, "%s: null wire %d", name, i);
+    // the narrow path loads dwords from in + (an offset that is a multiple of 4)
+    if (reinterpret_cast<uintptr_t>(in[i]) & 3u)
+      return set_error(DN_ERR_ARG, "%s: wire %d must be 4-byte aligned", name, i);
+    if (reinterpret_cast<uintptr_t>(offsets[i]) & 7u)
+      return set_error(DN_ERR_ARG, "%s: offsets of wire %d must be 8-byte aligned", name, i);
+    wire[i].in = in[i];
+    wire[i].in_bytes = in_bytes[i];
+    wire[i].offsets = offsets[i];
+    wire[i].x = xs[i];
+    if ((reinterpret_cast<uintptr_t>(in[i]) & 15u) == 0) *w16 |= 1u << i;
+  }
+  if (tune_env("DN_DECODE_W4") && tune_env("DN_DECODE_W4")[0] == '1') *w16 = 0u;
+  return DN_OK;
+}
+
 // Forward differences (split by additions) stay below 2^544 while
 // sum_{j<t} (n+t)^j < 2^23 (every table entry and every intermediate Newton
 // coefficient is bounded by f at some x <= n + t - 1); otherwise the split

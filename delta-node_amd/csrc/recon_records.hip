@@ -32,13 +32,6 @@ namespace rr {
 
 constexpr int kBlock = 256;
 
-struct Wire {
-  const uint8_t* in;        // packed records
-  uint64_t in_bytes;
-  const uint64_t* offsets;  // uint64[n_elem + 1]
-  uint64_t x;               // the abscissa every record should carry
-};
-
 struct Args {
   Wire wire[DN_MAX_RESOLVE];
   uint8_t* out_fe;
@@ -287,22 +280,7 @@ extern "C" int dn_m521_reconstruct_records(const uint8_t* const* in, const uint6
   if (blocks >= (1ull << 31)) return set_error(DN_ERR_ARG, "%s: n_elem %llu needs 2^31 workgroups or more", name,
                                                (unsigned long long)n_elem);
   rr::Args a{};
-  for (int i = 0; i < w->k; ++i) {
-    if (!in[i] || !offsets[i]) return set_error(DN_ERR_ARG, "%s: null wire %d", name, i);
-    // the narrow path loads dwords from in + (an offset that is a multiple of 4)
-    if (reinterpret_cast<uintptr_t>(in[i]) & 3u)
-      return set_error(DN_ERR_ARG, "%s: wire %d must be 4-byte aligned", name, i);
-    if (reinterpret_cast<uintptr_t>(offsets[i]) & 7u)
-      return set_error(DN_ERR_ARG, "%s: offsets of wire %d must be 8-byte aligned", name, i);
-    a.wire[i].in = in[i];
-    a.wire[i].in_bytes = in_bytes[i];
-    a.wire[i].offsets = offsets[i];
-    a.wire[i].x = xs[i];
-    if ((reinterpret_cast<uintptr_t>(in[i]) & 15u) == 0) a.w16 |= 1u << i;
-  }
-#ifdef DN_TUNING
-  if (tune_env("DN_DECODE_W4") && tune_env("DN_DECODE_W4")[0] == '1') a.w16 = 0u;  // A/B: 4-B staging
-#endif
+  if (const int rc = fill_wires(name, in, in_bytes, offsets, xs, w->k, a.wire, &a.w16)) return rc;
   a.out_fe = static_cast<uint8_t*>(out_fe);
   a.out_u64 = out_u64;
   a.overflow = overflow_count;
@@ -331,7 +309,5 @@ extern "C" int dn_m521_reconstruct_records(const uint8_t* const* in, const uint6
     case 17 * 4 + 1: rr::launch<17, 1>(w->k, g, s, a); break;
     default: rr::launch<17, 2>(w->k, g, s, a); break;
   }
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return set_error(DN_ERR_HIP, "%s: %s", name, hipGetErrorString(err));
-  return DN_OK;
+  return launch_status(name);
 }

@@ -1020,11 +1020,9 @@ static int cu_count() {
 // 2^24): same time as the full grid where the share buffer's placement is
 // fast, 4-5 % faster where it is slow (fewer writes in flight through the
 // L2 / EA path; DESIGN.md §5.1, profiles/r01/placement/).
-// DN_GRID_CAP overrides both (read per call; used by the tuning scripts).
+// DN_GRID_CAP overrides both (grid_cap(); used by the tuning scripts).
 static int grid_for(uint64_t ntiles, bool per_cu = false) {
-  const char* s = tune_env("DN_GRID_CAP");
-  const int v = s ? std::atoi(s) : 0;
-  const uint64_t cap = v > 0 ? static_cast<uint64_t>(v) : per_cu ? static_cast<uint64_t>(cu_count()) : 16384u;
+  const uint64_t cap = per_cu ? grid_cap(static_cast<uint64_t>(cu_count())) : grid_cap();
   const uint64_t blocks = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
   return static_cast<int>(blocks < cap ? blocks : cap);
 }
@@ -1040,7 +1038,9 @@ static uint32_t tile_map_for(int grid, bool allow_coop = true) {
   return m;
 }
 
-static int check_launch(const char* what) {
+// (declared in dn_internal.hpp, which keeps the HIP runtime include out: every unit's entry points link against
+// this definition)
+int launch_status(const char* what) {
   const hipError_t err = hipGetLastError();
   if (err != hipSuccess) return set_error(DN_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(err));
   return DN_OK;
@@ -1180,7 +1180,7 @@ static int split_common(SplitArgs a, int threshold, int n_shares, void* stream, 
     if (fold_each) launch_split_t<false, true>(threshold, g, s, a);
     else launch_split_t<false, false>(threshold, g, s, a);
   }
-  return check_launch(name);
+  return launch_status(name);
 }
 
 int device_cu_count() { return cu_count(); }
@@ -1311,7 +1311,7 @@ extern "C" int dn_m521_prng_coeffs(const uint32_t* key, uint64_t nonce, int roun
   const dim3 g(grid_for((a.ntiles + tp - 1) / tp));
   a.tile_map = tile_map_for(static_cast<int>(g.x), false);
   launch_prng_coeffs(tm1 + 1, g, static_cast<hipStream_t>(stream), a);
-  return check_launch("dn_m521_prng_coeffs");
+  return launch_status("dn_m521_prng_coeffs");
 }
 
 extern "C" int dn_m521_split_fe(const void* secrets_fe, const void* coeffs, void* shares, uint64_t n_elem,
@@ -1363,10 +1363,10 @@ extern "C" int dn_m521_reconstruct(const void* const* share_vecs, const dn_m521_
   if (rc != DN_OK) return rc;
   if (recon_low_route(a, w, out_u64 != nullptr, out_fe != nullptr, overflow_count != nullptr)) {
     launch_recon_low(w->k, g, s, a);
-    return check_launch(name);
+    return launch_status(name);
   }
   DN_RECON_DISPATCH(launch_recon_k, w, w->k, g, s, a)
-  return check_launch(name);
+  return launch_status(name);
 }
 
 // dn_m521_reconstruct over a list of vectors in one launch
@@ -1445,10 +1445,10 @@ extern "C" int dn_m521_reconstruct_many(const uint64_t* n_elem, const void* cons
   // (the counters are one pointer per call: asking for any keeps the full path)
   if (recon_low_route(a.r, w, out_u64 != nullptr, out_fe != nullptr, overflow_counts != nullptr)) {
     launch_recon_many_low(w->k, g, st, a);
-    return check_launch(name);
+    return launch_status(name);
   }
   DN_RECON_DISPATCH(launch_recon_many_k, w, w->k, g, st, a)
-  return check_launch(name);
+  return launch_status(name);
 }
 #undef DN_RECON_DISPATCH
 

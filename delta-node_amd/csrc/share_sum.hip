@@ -217,12 +217,9 @@ __global__ void __launch_bounds__(kSumBlock) share_sum_kernel(const ShareSumArgs
 }
 
 // Workgroups per launch: one wave per unit, each 4-wave workgroup striding
-// over the units, at most 16384 (as shamir_m521.hip grid_for; DN_GRID_CAP
-// overrides it in the tuning build).
+// over the units, at most grid_cap().
 static uint32_t sum_grid(uint64_t ntiles) {
-  const char* s = tune_env("DN_GRID_CAP");
-  const int v = s ? std::atoi(s) : 0;
-  const uint64_t cap = v > 0 ? static_cast<uint64_t>(v) : 16384u;
+  const uint64_t cap = grid_cap();
   const uint64_t blocks = (ntiles * kSumUnitsPerTile + kSumWaves - 1) / kSumWaves;
   return static_cast<uint32_t>(blocks < cap ? blocks : cap);
 }
@@ -261,8 +258,7 @@ extern "C" int dn_m521_sum_vecs(const void* const* vecs, const uint8_t* negate, 
     a.m = sum_plan_fill(addr.data(), negate, order.data(), m, o, j, ptrs, a.neg);
     for (uint32_t i = 0; i < a.m; ++i) a.in[i] = reinterpret_cast<const uint8_t*>(ptrs[i]);
     hipLaunchKernelGGL(share_sum_kernel, g, dim3(kSumBlock), 0, static_cast<hipStream_t>(stream), a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_error(DN_ERR_HIP, "%s: launch failed: %s", name, hipGetErrorString(err));
+    if (const int rc = launch_status(name)) return rc;
   }
   return DN_OK;
 }

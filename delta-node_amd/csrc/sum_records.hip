@@ -38,14 +38,14 @@ namespace sr {
 constexpr int kBlock = 256;
 constexpr int kGroup = DN_M521_SUM_RECORDS_GROUP;
 
-struct Wire {
+struct SumWire {  // (no x: one abscissa for the launch)
   const uint8_t* in;        // packed records
   uint64_t in_bytes;
   const uint64_t* offsets;  // uint64[n_elem + 1]
 };
 
 struct Args {
-  Wire wire[kGroup];
+  SumWire wire[kGroup];
   uint32_t neg[kGroup / 32];  // bit i of word i / 32: wire i is subtracted
   uint32_t w16[kGroup / 32];  // the same for: wire i is 16-B aligned (the wide staging path)
   const uint8_t* acc;         // tiled vector added to the sum, or null
@@ -270,8 +270,7 @@ extern "C" int dn_m521_sum_records(const uint8_t* const* in, const uint64_t* in_
     a.n_elem = n_elem;
     a.x = x;
     sr::launch(g, s, a);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return set_error(DN_ERR_HIP, "%s: %s", name, hipGetErrorString(err));
+    if (const int rc = launch_status(name)) return rc;
   }
   return DN_OK;
 }

@@ -23,6 +23,15 @@ namespace dn {
 
 typedef const __attribute__((address_space(4))) uint64_t* OffTab;  // read by scalar loads: no kernel writes offsets
 
+// One wire of a launch that knows each wire's abscissa, as it lies in the
+// kernel arguments (dn_internal.hpp fill_wires fills it).
+struct Wire {
+  const uint8_t* in;        // packed records
+  uint64_t in_bytes;
+  const uint64_t* offsets;  // uint64[n_elem + 1]
+  uint64_t x;               // the abscissa every record should carry
+};
+
 // A wave's window of one wire (wave-uniform): records e0 .. eN - 1 are bytes
 // [A, Bend), LDS byte 0 is A4 (the 16-B boundary at or below A where the wire
 // is 16-B aligned, w16, else the 4-B one), and `lds` says that the window fits

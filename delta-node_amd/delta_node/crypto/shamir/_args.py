@@ -42,6 +42,15 @@ def rows_of(block) -> list:
     return list(block.unbind(0)) if isinstance(block, torch.Tensor) and block.dim() == 2 else list(block)
 
 
+def check_share_vecs(what: str, vecs: Sequence, vb: int, dev) -> None:
+    """One tensor's share vectors: each a contiguous uint8 [vb] on dev."""
+    import torch
+
+    for v in vecs:
+        if v.dtype != torch.uint8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
+            raise ValueError(f"{what}: share vectors must be contiguous uint8 [{vb}] on {dev}")
+
+
 def check_out_form(what: str, out: str) -> None:
     if out not in ("int64", "field"):
         raise ValueError(f'{what}: out must be "int64" or "field"')

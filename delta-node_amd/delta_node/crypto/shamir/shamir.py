@@ -494,9 +494,7 @@ class SecretShare(object):
         self._check_abscissas(xs)
         dev = _device()
         vb = field.vec_bytes(n)
-        for v in vecs:
-            if v.dtype != torch.uint8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
-                raise ValueError(f"resolve_shares_vec: share vectors must be contiguous uint8 [{vb}] on {dev}")
+        _args.check_share_vecs("resolve_shares_vec", vecs, vb, dev)
         over = torch.zeros(1, dtype=torch.int32, device=dev) if return_overflow else None
         _args.check_out_form("resolve_shares_vec", out)
         res, out_fe, out_u64 = _args.result(out, n, vb, dev)
@@ -531,21 +529,8 @@ class SecretShare(object):
         self._require_m521()
         import torch
 
-        what = "check_shares_vec"
-        vecs = _args.rows_of(shares)
-        xs = [int(x) for x in xs]
-        if len(vecs) != len(xs):
-            raise ValueError("check_shares_vec: one abscissa per share vector")
-        self._check_abscissas(xs)
-        if not all(_args.fits_u64(x) for x in xs):
-            raise NotImplementedError("check_shares_vec: abscissas must fit 64 bits")
-        plan = _native.check_plan(xs, self.threshold)
-        dev = _device()
-        vb = field.vec_bytes(n)
-        for v in vecs:
-            if v.dtype != torch.uint8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
-                raise ValueError(f"check_shares_vec: share vectors must be contiguous uint8 [{vb}] on {dev}")
-        _args.check_bad_flag(what, bad, dev, "share vectors")
+        vecs, xs, dev, vb, plan = self._checked_rows("check_shares_vec", shares, xs, n, bad,
+                                                     lambda xs: _native.check_plan(xs, self.threshold))
         bad, checked = _args.bad_flag(bad, dev)
         marks = torch.empty(n, dtype=torch.uint8, device=dev) if culprit else None
         _native.check_shares(vecs, plan, bad, marks, n)
@@ -587,21 +572,13 @@ class SecretShare(object):
         import torch
 
         what = "resolve_shares_vec_robust"
-        vecs = _args.rows_of(shares)
-        xs = [int(x) for x in xs]
-        if len(vecs) != len(xs):
-            raise ValueError(f"{what}: one abscissa per share vector")
-        self._check_abscissas(xs)
-        if not all(_args.fits_u64(x) for x in xs):
-            raise NotImplementedError(f"{what}: abscissas must fit 64 bits")
-        plan = _native.robust_plan(xs, self.threshold)
-        _args.check_out_form(what, out)
-        dev = _device()
-        vb = field.vec_bytes(n)
-        for v in vecs:
-            if v.dtype != torch.uint8 or v.numel() != vb or v.device != dev or not v.is_contiguous():
-                raise ValueError(f"{what}: share vectors must be contiguous uint8 [{vb}] on {dev}")
-        _args.check_bad_flag(what, bad, dev, "share vectors")
+
+        def plan_of(xs):
+            plan = _native.robust_plan(xs, self.threshold)
+            _args.check_out_form(what, out)
+            return plan
+
+        vecs, xs, dev, vb, plan = self._checked_rows(what, shares, xs, n, bad, plan_of)
         bad, checked = _args.bad_flag(bad, dev)
         marks = torch.empty(n, dtype=torch.uint8, device=dev) if culprit else None
         res, out_fe, out_u64 = _args.result(out, n, vb, dev)
@@ -651,28 +628,8 @@ class SecretShare(object):
         from . import codec
 
         what = "resolve_records_vec"
-        recs = _args.wire_pairs(what, records)
-        if xs is not None:
-            xs = [int(x) for x in xs]
-            if len(recs) != len(xs):
-                raise ValueError("resolve_records_vec: one abscissa per wire")
-            self._check_abscissas(xs)
-        elif not recs:
-            raise ValueError("not enough values to unpack (expected 2, got 0)")
-        _args.check_out_form(what, out)
-        n = int(n)
-        if n < 0:
-            raise ValueError("resolve_records_vec: n must not be negative")
-        first = _args.check_wires(what, recs, n)
-        _args.check_bad_flag(what, bad, first, "records")
-        if xs is None and n == 0:
-            raise ValueError("resolve_records_vec: xs=None needs a first record to read each abscissa from")
-        dev = _device()
-        if first != dev:
-            raise ValueError(f"resolve_records_vec: records must be on {dev}")
-        if xs is None:
-            xs = _first_record_xs(recs)
-            self._check_abscissas(xs)
+        recs, xs, n, dev, _ = self._checked_wires(what, records, xs, n, [(what, bad)], self._check_abscissas,
+                                                  lambda: _args.check_out_form(what, out))
         k = len(xs)
         bad, checked = _args.bad_flag(bad, dev)
         over = torch.zeros(1, dtype=torch.int32, device=dev) if return_overflow else None
@@ -738,36 +695,15 @@ class SecretShare(object):
         from . import codec
 
         what = "check_records_vec"
-        recs = _args.wire_pairs(what, records)
 
         def plan_of(xs):
             self._check_abscissas(xs)
             if not all(_args.fits_u64(x) for x in xs):
-                raise NotImplementedError("check_records_vec: abscissas must fit 64 bits")
+                raise NotImplementedError(f"{what}: abscissas must fit 64 bits")
             return _native.check_plan(xs, self.threshold)
 
-        plan = None
-        if xs is not None:
-            xs = [int(x) for x in xs]
-            if len(recs) != len(xs):
-                raise ValueError("check_records_vec: one abscissa per wire")
-            plan = plan_of(xs)
-        elif not recs:
-            raise ValueError("not enough values to unpack (expected 2, got 0)")
-        n = int(n)
-        if n < 0:
-            raise ValueError("check_records_vec: n must not be negative")
-        first = _args.check_wires(what, recs, n)
-        _args.check_bad_flag(what, bad, first, "records")
-        _args.check_bad_flag(what + ": bad_records", bad_records, first, "records")
-        if xs is None and n == 0:
-            raise ValueError("check_records_vec: xs=None needs a first record to read each abscissa from")
-        dev = _device()
-        if first != dev:
-            raise ValueError(f"check_records_vec: records must be on {dev}")
-        if xs is None:
-            xs = _first_record_xs(recs, what)
-            plan = plan_of(xs)
+        flags = [(what, bad), (what + ": bad_records", bad_records)]
+        recs, xs, n, dev, plan = self._checked_wires(what, records, xs, n, flags, plan_of)
         bad, checked = _args.bad_flag(bad, dev)
         bad_records, records_checked = _args.bad_flag(bad_records, dev)
         marks = torch.empty(n, dtype=torch.uint8, device=dev) if culprit else None
@@ -777,6 +713,61 @@ class SecretShare(object):
             codec.check_bad_records(bad_records, what)
         count = int(bad[0].item()) if checked else None
         return (count, marks) if culprit else count
+
+    def _checked_rows(self, what: str, shares, xs, n: int, bad, plan_of) -> tuple:
+        """The preamble of the calls that check k tiled share vectors:
+        `resolve_shares_vec`'s checks on the rows and abscissas, the 64-bit
+        fit, plan_of(xs) (the launch's plan, with whatever else the method
+        checks at that place), then each vector's form and the bad flag's.
+        Returns (vecs, xs, dev, vb, plan)."""
+        vecs = _args.rows_of(shares)
+        xs = [int(x) for x in xs]
+        if len(vecs) != len(xs):
+            raise ValueError(f"{what}: one abscissa per share vector")
+        self._check_abscissas(xs)
+        if not all(_args.fits_u64(x) for x in xs):
+            raise NotImplementedError(f"{what}: abscissas must fit 64 bits")
+        plan = plan_of(xs)
+        dev = _device()
+        vb = field.vec_bytes(n)
+        _args.check_share_vecs(what, vecs, vb, dev)
+        _args.check_bad_flag(what, bad, dev, "share vectors")
+        return vecs, xs, dev, vb, plan
+
+    def _checked_wires(self, what: str, records, xs, n, flags, on_xs, before_n=None) -> tuple:
+        """The preamble of the calls that read k wires: the (packed, offsets)
+        pairs, the abscissas given or (xs=None) read from each wire's first
+        record once the wires are known to be on the device, n, the wires'
+        form and the form of every (label, flag) of `flags`.  on_xs(xs) runs
+        where the abscissas become known (either place) and before_n() between
+        the abscissas and n: the checks the method interleaves.  Returns
+        (recs, xs, n, dev, on_xs's result)."""
+        recs = _args.wire_pairs(what, records)
+        got = None
+        if xs is not None:
+            xs = [int(x) for x in xs]
+            if len(recs) != len(xs):
+                raise ValueError(f"{what}: one abscissa per wire")
+            got = on_xs(xs)
+        elif not recs:
+            raise ValueError("not enough values to unpack (expected 2, got 0)")
+        if before_n is not None:
+            before_n()
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"{what}: n must not be negative")
+        first = _args.check_wires(what, recs, n)
+        for label, flag in flags:
+            _args.check_bad_flag(label, flag, first, "records")
+        if xs is None and n == 0:
+            raise ValueError(f"{what}: xs=None needs a first record to read each abscissa from")
+        dev = _device()
+        if first != dev:
+            raise ValueError(f"{what}: records must be on {dev}")
+        if xs is None:
+            xs = _first_record_xs(recs, what)
+            got = on_xs(xs)
+        return recs, xs, n, dev, got
 
     def _check_abscissas(self, xs: Sequence[int]) -> None:
         """resolve_shares' checks on the abscissas (shamir.py:70-83), with its messages."""

@@ -30,6 +30,10 @@ GEOM = ("kMaxRecord", "kWinPad", "kDecWindow", "kWinLimit", "kDecRowWords", "kEn
 FUNCS = ("win_of", "stage_load", "stage_store", "stage_direct", "parse_lds", "parse_global", "lds_order", "limb_bytes",
          "y_len", "lds_put_bytes", "lay_y", "flush_window", "scan_slot", "scan_block_totals", "scan_passes",
          "scan_count")
+# the pieces the tiled-row check family and the launches share
+ROWS = {"rows_load": "share_rows.hpp", "rows_accumulate": "share_rows.hpp", "rows_walk": "share_rows.hpp",
+        "verdict_count": "share_rows.hpp", "syndrome_weights": "share_rows.hpp", "weights_fill": "share_rows.hpp",
+        "grid_cap": "dn_internal.hpp", "fill_wires": "dn_internal.hpp"}
 
 
 @pytest.fixture(scope="module")
@@ -84,6 +88,14 @@ def test_every_constant_and_shared_function_is_defined_once():
                          r"static|inline|constexpr|DN_WIRE_HD)\s+)+[\w:<>]+[\s*&]+" + name + r"\s*\(", flags=re.M)
         where = [f for f, text in src.items() if pat.search(text)]
         assert len(where) == 1 and where[0] in ("wire_geom.hpp", "wire_parse.hpp", "wire_emit.hpp"), (name, where)
+    for name, home in ROWS.items():
+        pat = re.compile(r"^[ \t]*(?:template\s*<[^>]*>\s*)?(?:(?:__device__|__forceinline__|static|inline)\s+)*"
+                         r"[\w:<>]+[\s*&]+" + name + r"\s*\([^;{]*\{", flags=re.M)
+        assert [f for f, text in src.items() if pat.search(text)] == [home], name
+    # (among the receiving units, which include the parser; codec_many.hip's Wire is the encoder's, another thing)
+    readers = {f: text for f, text in src.items() if f == "wire_parse.hpp" or '#include "wire_parse.hpp"' in text}
+    assert [f for f, text in readers.items() if re.search(r"\bstruct\s+Wire\b", text)] == ["wire_parse.hpp"]
+    assert [f for f, text in src.items() if re.search(r"\bstruct\s+CheckWeights\b", text)] == ["share_rows.hpp"]
     # the old names of the same things are gone
     for text in src.values():
-        assert not re.search(r"\bkFrameMaxRecord\b|\bparse_record_global\b", text)
+        assert not re.search(r"\bkFrameMaxRecord\b|\bparse_record_global\b|\b(check|robust)_(load|add|grid)\b", text)

@@ -18,7 +18,10 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "delta-node_amd")
 SRCS = ["shamir_m521", "codec_m521", "aes_envelope", "mask_pcg64", "sum_i64", "mimc7_bn254", "mt19937_device",
-        "share_sum", "recon_records", "codec_many", "sum_records", "codec_frame"]
+        "share_sum", "recon_records", "codec_many", "sum_records", "codec_frame", "commit_sha256", "share_check",
+        "check_records", "share_robust"]
+# the flags the Makefile gives one unit beyond the common ones
+EXTRA = {"share_robust": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
@@ -47,7 +50,7 @@ def main() -> int:
         for src in SRCS:
             out = os.path.join(td, src + ".s")
             subprocess.run([HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "-I" + os.path.join(PKG, "..", "include"),
-                            "-I" + os.path.join(PKG, "csrc"), "-S", "--cuda-device-only",
+                            "-I" + os.path.join(PKG, "csrc"), *EXTRA.get(src, []), "-S", "--cuda-device-only",
                             os.path.join(PKG, "csrc", src + ".hip"), "-o", out], check=True)
             hits, info = scan(open(out).read())
             for k, v in sorted(info.items()):
