@@ -3,40 +3,23 @@ against fractions.Fraction, the kernel's finish (csrc/robust_core.hpp) in a
 stand-alone program, built plainly and under ASan + UBSan, against the definition
 in Python integers; refusals by code and message; the method's argument errors."""
 import math
-import os
-import shutil
-import subprocess
 from fractions import Fraction
 
 import pytest
 import torch
 
+import host_program
 import share_robust_cases as robust
 from delta_node.crypto import shamir
 from delta_node.crypto.shamir import _native, field
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = robust.P
 
 
-@pytest.fixture(scope="module", params=[[], ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]],
-                ids=["plain", "sanitized"])
+@pytest.fixture(scope="module", params=[[], host_program.SANITIZE], ids=["plain", "sanitized"])
 def program(request, tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++")
-    assert cxx, "no system C++ compiler"
-    exe = str(tmp_path_factory.mktemp("resolve_robust") / "robust_core_check")
-    cmd = [cxx, "-std=c++17", "-O1", "-g", *request.param, "-I", os.path.join(ROOT, "delta-node_amd", "csrc"), "-I",
-           os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "host", "robust_core_check.cpp"), "-o", exe]
-    build = subprocess.run(cmd, capture_output=True, text=True)
-    assert build.returncode == 0, build.stderr
-
-    def run(t, xs, rows=()):
-        lines = [f"{t} {len(xs)} " + " ".join(map(str, xs))] + [" ".join(f"{y:x}" for y in ys) for ys in rows]
-        done = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=120)
-        assert done.returncode == 0, done.stdout + done.stderr
-        return done.stdout.splitlines()
-
-    return run
+    run = host_program.compile_program(tmp_path_factory.mktemp("resolve_robust"), "robust_core_check", request.param)
+    return lambda t, xs, rows=(): run(host_program.share_lines(t, xs, rows))
 
 
 @pytest.mark.parametrize("t, xs", robust.CASES + robust.MORE)
