@@ -158,6 +158,8 @@ _SYMBOLS = {
     "dn_m521_check_records": (i32, [pvp, pu64, pvp, pu64, ctypes.POINTER(CheckPlan), vp, vp, vp, u64, vp], False),
     "dn_m521_robust_plan": (i32, [pu64, i32, i32, ctypes.POINTER(RobustPlan)], False),
     "dn_m521_reconstruct_robust": (i32, [pvp, ctypes.POINTER(RobustPlan), vp, vp, vp, vp, u64, vp], False),
+    "dn_m521_reconstruct_records_robust": (i32, [pvp, pu64, pvp, pu64, ctypes.POINTER(RobustPlan), vp, vp, vp, vp, vp,
+                                                 u64, vp], False),
 }
 EXPORTS = tuple(_SYMBOLS)
 
@@ -515,6 +517,22 @@ def reconstruct_robust(share_vecs: Sequence, plan: RobustPlan, counts, out_fe=No
     ptrs = (ctypes.c_void_p * k)(*[v.data_ptr() for v in share_vecs])
     check(L.dn_m521_reconstruct_robust(ptrs, ctypes.byref(plan), _ptr(out_fe), _ptr(out_u64), _ptr(counts),
                                        _ptr(culprit), n, stream_ptr()))
+
+
+def reconstruct_records_robust(wires: Sequence, xs: Sequence[int], plan: RobustPlan, counts, bad, out_fe=None,
+                               out_u64=None, culprit=None, n: int = 0) -> None:
+    """`reconstruct_robust` straight over plan.check.k wires
+    (dn_m521_reconstruct_records_robust): wires, xs and bad as
+    `check_records`, the outputs, counts and culprit as `reconstruct_robust`.
+    Does not synchronise."""
+    L = need(lib(), "dn_m521_reconstruct_records_robust")
+    k = len(wires)
+    if k != plan.check.k or k != len(xs):
+        raise ValueError("reconstruct_records_robust: one wire and one abscissa per share of the plan")
+    check(L.dn_m521_reconstruct_records_robust(*_wire_arrays(wires),
+                                               (ctypes.c_uint64 * max(k, 1))(*[int(x) for x in xs]),
+                                               ctypes.byref(plan), _ptr(out_fe), _ptr(out_u64), _ptr(counts),
+                                               _ptr(culprit), _ptr(bad), n, stream_ptr()))
 
 
 def mt_draw_coeffs(rng, n: int, tm1: int) -> np.ndarray:

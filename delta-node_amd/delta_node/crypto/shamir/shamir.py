@@ -714,6 +714,63 @@ class SecretShare(object):
         count = int(bad[0].item()) if checked else None
         return (count, marks) if culprit else count
 
+    def resolve_records_vec_robust(self, records, xs: Optional[Sequence[int]], n: int, *, out: str = "int64",
+                                   culprit: bool = False, bad=None, bad_records=None):
+        """`resolve_shares_vec_robust` straight from wire records: the secret
+        of every element from k >= threshold + 2 wires, past ONE damaged wire
+        per element, in one launch and without the k decoded vectors
+        (dn_m521_reconstruct_records_robust).  What a receiver whose peer sent
+        one truncated or garbled wire calls instead of `check_records_vec`
+        followed by `resolve_records_vec`: a record that cannot be represented
+        counts as y = 0, so its wire is located as the culprit and the secret
+        comes from the other wires.
+
+        records, xs, n, bad_records  as `check_records_vec` (xs=None takes each
+                 wire's x from its first record: the one form that synchronises
+                 before the launch), with its checks, messages and exception
+                 types, all before any device use
+        out, culprit, bad  as `resolve_shares_vec_robust`, and its return:
+                 (result, count) or (result, count, culprit), count the pair of
+                 ints (inconsistent, corrected), or None where bad is given
+        The call synchronises only where bad or bad_records is None; with both
+        given (and xs given) it can be captured into a graph.
+
+        Values, both counts and every culprit byte are those of
+        decode_share_vec on every wire followed by resolve_shares_vec_robust,
+        bit for bit; the two record counts are those of resolve_records_vec on
+        the same wires.
+
+        NotImplementedError for resolve_shares_vec_robust's limits — fewer than
+        2 or more than 4 spare shares, more than 16 wires, an abscissa 0 or one
+        past 64 bits, a weight of 2^32 or more, a divisor's odd part of 2^16 or
+        more — with no decode fallback.  There is no CPU fallback."""
+        self._require_m521()
+        import torch
+
+        from . import codec
+
+        what = "resolve_records_vec_robust"
+
+        def plan_of(xs):
+            self._check_abscissas(xs)
+            if not all(_args.fits_u64(x) for x in xs):
+                raise NotImplementedError(f"{what}: abscissas must fit 64 bits")
+            return _native.robust_plan(xs, self.threshold)
+
+        flags = [(what, bad), (what + ": bad_records", bad_records)]
+        recs, xs, n, dev, plan = self._checked_wires(what, records, xs, n, flags, plan_of,
+                                                     lambda: _args.check_out_form(what, out))
+        bad, checked = _args.bad_flag(bad, dev)
+        bad_records, records_checked = _args.bad_flag(bad_records, dev)
+        marks = torch.empty(n, dtype=torch.uint8, device=dev) if culprit else None
+        res, out_fe, out_u64 = _args.result(out, n, field.vec_bytes(n), dev)
+        recs, wires = _args.aligned_wires(recs)
+        _native.reconstruct_records_robust(wires, xs, plan, bad, bad_records, out_fe, out_u64, marks, n)
+        if records_checked:
+            codec.check_bad_records(bad_records, what)
+        count = tuple(bad.tolist()) if checked else None
+        return (res, count, marks) if culprit else (res, count)
+
     def _checked_rows(self, what: str, shares, xs, n: int, bad, plan_of) -> tuple:
         """The preamble of the calls that check k tiled share vectors:
         `resolve_shares_vec`'s checks on the rows and abscissas, the 64-bit

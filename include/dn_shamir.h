@@ -735,6 +735,38 @@ int dn_m521_reconstruct_robust(const void* const* share_vecs, const dn_m521_robu
                                uint64_t n_elem, void* stream);
 
 /*
+ * The robust reconstruct straight from wire records: what a receiver with one
+ * damaged wire of k >= t + 2 runs instead of dn_m521_check_records followed by
+ * dn_m521_reconstruct_records, in one launch.  Values, `counts` and every
+ * `culprit` byte are those of dn_m521_decode_shares on every wire followed by
+ * dn_m521_reconstruct_robust, bit for bit and without the k intermediate tiled
+ * vectors; `bad_counts` are those of dn_m521_reconstruct_records on the same
+ * wires.  A record the decoder cannot represent contributes y = 0 and is
+ * counted: its wire is then located like any other bad share, and the element's
+ * secret comes from the other wires.
+ *   in, in_bytes, offsets, xs  HOST arrays of plan->check.k entries, as for
+ *                 dn_m521_check_records, in the order of the plan's abscissas
+ *   plan          dn_m521_robust_plan's for xs
+ *   out_fe / out_u64, counts, culprit  as for dn_m521_reconstruct_robust
+ *   bad_counts    DEVICE uint32[2], ADDED to, as for dn_m521_check_records
+ * Nothing outside in[i][0, in_bytes[i]) and offsets[i][0, n_elem] is read, and
+ * nothing is read or written for elements at or past n_elem (the padding lanes
+ * of out_fe's last tile included).  n_elem == 0 returns DN_OK and touches no
+ * pointer.  DN_ERR_ARG, before any device call: a null pointer, both or neither
+ * of the outputs, a malformed plan, a wire that is not 4-byte aligned, offsets
+ * that are not 8-byte aligned, 2^31 workgroups (of 256 elements) or more.  The
+ * wire descriptors and the plan travel in the kernel arguments: no device
+ * table, no staging buffer.  Does not synchronise `stream`; can be captured
+ * into a graph.
+ * Replaces shamir.py:68-90 over records parsed by :36-45, past one bad share.
+ */
+int dn_m521_reconstruct_records_robust(const uint8_t* const* in, const uint64_t* in_bytes,
+                                       const uint64_t* const* offsets, const uint64_t* xs,
+                                       const dn_m521_robust_plan_t* plan, void* out_fe, int64_t* out_u64,
+                                       uint32_t* counts /*[2]*/, uint8_t* culprit /*[n_elem] or NULL*/,
+                                       uint32_t* bad_counts /*[2]*/, uint64_t n_elem, void* stream);
+
+/*
  * Sum of share wires: the party-side step of share-domain aggregation taken
  * straight from the records.  Party x holds share x of every member's tensor
  * as m wires (dn_m521_encode_shares' output: records [len(xb)][xb][yb] back to

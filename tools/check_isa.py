@@ -19,9 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "delta-node_amd")
 SRCS = ["shamir_m521", "codec_m521", "aes_envelope", "mask_pcg64", "sum_i64", "mimc7_bn254", "mt19937_device",
         "share_sum", "recon_records", "codec_many", "sum_records", "codec_frame", "commit_sha256", "share_check",
-        "check_records", "share_robust"]
+        "check_records", "share_robust", "robust_records"]
 # the flags the Makefile gives one unit beyond the common ones
-EXTRA = {"share_robust": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+NOPK = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA = {"share_robust": NOPK, "robust_records": NOPK}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
