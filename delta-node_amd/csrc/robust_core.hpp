@@ -9,7 +9,11 @@
 //   share i located             N = |w_i| canon(T') + |A_i| (p - canon(S_0))
 //                               (< 2^554: the same 18 limbs, the same
 //                               multiply-add), f = canon(N) / (|w_i| D_all);
-//   k even                      f = p - f.
+//   k even                      f = p - f;
+//   shares i < j located        (two errors, r = 4) robust_pair.hpp, where the
+//                               signs are derived the same way: A_l / w_l =
+//                               (-1)^(k-1) |A_l| / |w_l|, and the sign of
+//                               x_j - x_i decides whether f gains or loses.
 // A division by d 2^e, d odd and below 2^16, is exact_div_small's (add the m p
 // that makes the value divisible by d, m = -r p^{-1} mod d; divide limb by
 // limb from the low end with d^{-1} mod 2^32; the quotient is canonical) and a

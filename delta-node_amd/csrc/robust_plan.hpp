@@ -118,9 +118,52 @@ inline int robust_plan_build(const uint64_t* xs, int k, int threshold, dn_m521_r
   return DN_OK;
 }
 
+// What the pair test and the pair correction (robust_pair.hpp) ask of the abscissas:
+// per pair, x_i + x_j and x_i x_j below 2^32 (one-limb multipliers) and an odd part of |x_j - x_i| below
+// 2^16 (the one division whose constants the kernel computes itself).  (Behind check_plan_build at
+// r = 4 none of them can fire, x_i^3 <= c[3][i] < 2^32 being the stronger bound; they are stated and
+// checked on their own so that the finish does not lean on a bound made for something else.)
+inline int robust_pair_bounds(const uint64_t* xs, int k, char* why, size_t why_len) {
+  auto fail = [&](const char* msg) {
+    snprintf(why, why_len, "%s", msg);
+    return DN_ERR_UNSUPPORTED;
+  };
+  for (int j = 1; j < k; ++j)
+    for (int i = 0; i < j; ++i) {
+      if (xs[i] >= kCheckMaxC || xs[j] >= kCheckMaxC || xs[i] + xs[j] >= kCheckMaxC || xs[i] * xs[j] >= kCheckMaxC)
+        return fail("dn_m521_robust_plan2: x_i + x_j or x_i x_j of 2^32 or more (the pair test's one-limb bound)");
+      uint64_t d = xs[j] > xs[i] ? xs[j] - xs[i] : xs[i] - xs[j];
+      while (d && (d & 1) == 0) d >>= 1;
+      if (d >= kRobustMaxD)
+        return fail("dn_m521_robust_plan2: a difference x_j - x_i with an odd part of 2^16 or more (one exact division)");
+    }
+  return DN_OK;
+}
+
+// robust_plan_build for `errors` bad shares per element (dn_m521_robust_plan2).  errors == 1 is
+// robust_plan_build; errors == 2 also needs r == 4 and robust_pair_bounds, and records the mode in
+// out->max_errors.
+inline int robust_plan_build2(const uint64_t* xs, int k, int threshold, int errors, dn_m521_robust_plan_t* out,
+                              char* why, size_t why_len) {
+  auto fail = [&](int code, const char* msg) {
+    snprintf(why, why_len, "%s", msg);
+    return code;
+  };
+  if (errors != 1 && errors != 2) return fail(DN_ERR_ARG, "dn_m521_robust_plan2: errors must be 1 or 2");
+  int rc = robust_plan_build(xs, k, threshold, out, why, why_len);
+  if (rc != DN_OK || errors == 1) return rc;
+  if (out->check.r != 4)
+    return fail(DN_ERR_UNSUPPORTED,
+                "dn_m521_robust_plan2: two errors per element need exactly four spare shares (k == threshold + 4)");
+  if ((rc = robust_pair_bounds(xs, k, why, why_len)) != DN_OK) return rc;
+  out->max_errors = 2u;
+  return DN_OK;
+}
+
 // What the device entry point requires of a plan it did not build.
 inline bool robust_plan_wellformed(const dn_m521_robust_plan_t& p) {
   if (!check_plan_wellformed(p.check) || p.check.r < 2 || p.negate > 1u) return false;
+  if (p.max_errors > 2u || (p.max_errors == 2u && p.check.r != 4)) return false;
   for (int i = 0; i <= DN_MAX_RESOLVE; ++i) {
     if (i >= p.check.k && i != kRobustAll) continue;
     const dn_m521_div_small_t& q = p.div[i];

@@ -36,6 +36,10 @@
 // accumulators are the only state carried from wire to wire; the finish starts
 // after the last wire's staging registers are dead.
 //
+// The two-error form (TWO) adds robust_pair.hpp's
+// wave-cooperative pair search after the verdict, in the wave's LDS slice,
+// which is free once the last wire is parsed.
+//
 // Everything a launch needs travels in its arguments (about 2.8 KB): no device
 // table, no staging buffer, nothing to synchronise.  Lanes at or past n_elem
 // read and write nothing, the padding lanes of a field output's last tile
@@ -44,6 +48,7 @@
 
 #include "dn_internal.hpp"
 #include "robust_core.hpp"
+#include "robust_pair.hpp"
 #include "robust_plan.hpp"
 #include "share_rows.hpp"
 #include "wire_parse.hpp"
@@ -121,9 +126,11 @@ __device__ __forceinline__ void wire_step(const Args& a, uint32_t i, const uint3
 
 // R = 2 (3-of-5 with all five wires) is held to the registers of three waves per SIMD: 177 -> 168
 // VGPRs, still without scratch; R = 3 and 4 need 196 and 214 and stay at two.
-template <int R, int OUT>
+template <int R, int OUT, bool TWO = false>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(R == 2 ? 3 : 2)))
 robust_records_kernel(const Args a) {
+  static_assert(!TWO || R == 4, "two errors are located from four syndromes");
+  static_assert(kPairWords <= kDecRowWords, "the pair search reuses the wave's window slice");
   __shared__ __attribute__((aligned(16))) uint32_t s_win[kBlock / 64][kDecRowWords];
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -172,6 +179,7 @@ robust_records_kernel(const Args a) {
         check_verdict<R>(robust_syndromes<R>(S), static_cast<int>(k), [&a](int j, int s) { return a.wt.xp[j][s]; });
     if (verdict >= kChkUnexplained) robust_plain(S[R], a.div[kRobustAll], a.negate, f);
   }
+  if constexpr (TWO) robust_pair_wave(a, s_win[wv], S, verdict, f);
   // the correction, wave-uniform: candidate i's constants in SGPRs, a candidate without lanes skipped
   if (__ballot(verdict < kChkUnexplained) != 0ull) {
 #pragma unroll 1
@@ -199,7 +207,8 @@ static void launch(int r, dim3 g, hipStream_t s, const Args& a) {
   switch (r) {
     case 2: hipLaunchKernelGGL((robust_records_kernel<2, OUT>), g, dim3(kBlock), 0, s, a); break;
     case 3: hipLaunchKernelGGL((robust_records_kernel<3, OUT>), g, dim3(kBlock), 0, s, a); break;
-    default: hipLaunchKernelGGL((robust_records_kernel<4, OUT>), g, dim3(kBlock), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((robust_records_kernel<4, OUT>), g, dim3(kBlock), 0, s, a); break;
+    default: hipLaunchKernelGGL((robust_records_kernel<4, OUT, true>), g, dim3(kBlock), 0, s, a); break;  // two errors
   }
 }
 
@@ -241,7 +250,8 @@ extern "C" int dn_m521_reconstruct_records_robust(const uint8_t* const* in, cons
   a.negate = plan->negate;
   const dim3 g(static_cast<uint32_t>(blocks));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (out_fe) rr::launch<rr::kField>(chk.r, g, s, a);
-  else rr::launch<rr::kInt64>(chk.r, g, s, a);
+  const int form = plan->max_errors == 2u ? 5 : chk.r;  // (wellformed: two errors only with r == 4)
+  if (out_fe) rr::launch<rr::kField>(form, g, s, a);
+  else rr::launch<rr::kInt64>(form, g, s, a);
   return launch_status(name);
 }

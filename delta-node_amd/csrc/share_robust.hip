@@ -24,6 +24,13 @@
 // the wave's lanes has by a scalar branch, and a wave without a located lane
 // skips the loop.  On clean data no lane enters it.
 //
+// The two-error form (TWO, a plan of dn_m521_robust_plan2 with errors == 2;
+// DESIGN.md §4.31) then takes the elements left unexplained through the
+// wave-cooperative pair search of robust_pair.hpp: the element's four
+// canonical syndromes go through 272 bytes of LDS per wave, the wave's lanes
+// test one pair each, the owning lane corrects.  A wave without such an element
+// pays one ballot; the one-error instantiations hold none of it.
+//
 // Everything a launch needs travels in its arguments (about 2.4 KB): no device
 // table, no staging buffer, nothing to synchronise.  Lanes at or past n_elem
 // are masked off for the whole body.
@@ -31,6 +38,7 @@
 
 #include "dn_internal.hpp"
 #include "robust_core.hpp"
+#include "robust_pair.hpp"
 #include "robust_plan.hpp"
 #include "share_rows.hpp"
 
@@ -52,8 +60,9 @@ static_assert(sizeof(RobustArgs) <= 4096, "the launch's constants ride in the 4 
 
 enum RobustOut { kRobustField, kRobustInt64 };
 
-template <int R, int OUT>
+template <int R, int OUT, bool TWO = false>
 __global__ void __launch_bounds__(kRowsBlock) robust_kernel(const RobustArgs a) {
+  static_assert(!TWO || R == 4, "two errors are located from four syndromes");
   // rows_walk's loop, written out: with this body as its lambda the field form's registers are
   // allocated otherwise (235 -> 219 VGPRs at R = 4) and it runs 1.7 % slower
   const uint32_t lane = threadIdx.x & 63u;
@@ -74,10 +83,14 @@ __global__ void __launch_bounds__(kRowsBlock) robust_kernel(const RobustArgs a) 
           return syndrome_weights<R>(a.wt, i, c);
         },
         [&a](uint32_t i) { return a.shares[i]; }, k, tile, w, S);
-    const uint8_t verdict =
+    uint8_t verdict =
         check_verdict<R>(robust_syndromes<R>(S), static_cast<int>(k), [&a](int j, int s) { return a.wt.xp[j][s]; });
     uint32_t f[kChkLimbs];
     if (verdict >= kChkUnexplained) robust_plain(S[R], a.div[kRobustAll], a.negate, f);
+    if constexpr (TWO) {  // the pairs: a wave's window is its own, so no workgroup barrier
+      __shared__ uint32_t s_pair[kRowsBlock / 64][kPairWords];
+      robust_pair_wave(a, s_pair[q], S, verdict, f);
+    }
     // the correction, wave-uniform: candidate i's constants in SGPRs, a candidate without lanes skipped
     if (__ballot(verdict < kChkUnexplained) != 0ull) {
 #pragma unroll 1
@@ -104,7 +117,8 @@ static void launch_robust(int r, dim3 g, hipStream_t s, const RobustArgs& a) {
   switch (r) {
     case 2: hipLaunchKernelGGL((robust_kernel<2, OUT>), g, dim3(kRowsBlock), 0, s, a); break;
     case 3: hipLaunchKernelGGL((robust_kernel<3, OUT>), g, dim3(kRowsBlock), 0, s, a); break;
-    default: hipLaunchKernelGGL((robust_kernel<4, OUT>), g, dim3(kRowsBlock), 0, s, a); break;
+    case 4: hipLaunchKernelGGL((robust_kernel<4, OUT>), g, dim3(kRowsBlock), 0, s, a); break;
+    default: hipLaunchKernelGGL((robust_kernel<4, OUT, true>), g, dim3(kRowsBlock), 0, s, a); break;  // two errors
   }
 }
 
@@ -115,6 +129,13 @@ using namespace dn;
 extern "C" int dn_m521_robust_plan(const uint64_t* xs, int k, int threshold, dn_m521_robust_plan_t* out) {
   char why[160] = "";
   const int rc = robust_plan_build(xs, k, threshold, out, why, sizeof(why));
+  return rc == DN_OK ? DN_OK : set_error(rc, "%s", why);
+}
+
+extern "C" int dn_m521_robust_plan2(const uint64_t* xs, int k, int threshold, int errors,
+                                    dn_m521_robust_plan_t* out) {
+  char why[160] = "";
+  const int rc = robust_plan_build2(xs, k, threshold, errors, out, why, sizeof(why));
   return rc == DN_OK ? DN_OK : set_error(rc, "%s", why);
 }
 
@@ -147,7 +168,8 @@ extern "C" int dn_m521_reconstruct_robust(const void* const* share_vecs, const d
   a.negate = plan->negate;
   const dim3 g(rows_grid(ntiles));
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (out_fe) launch_robust<kRobustField>(chk.r, g, s, a);
-  else launch_robust<kRobustInt64>(chk.r, g, s, a);
+  const int form = plan->max_errors == 2u ? 5 : chk.r;  // (wellformed: two errors only with r == 4)
+  if (out_fe) launch_robust<kRobustField>(form, g, s, a);
+  else launch_robust<kRobustInt64>(form, g, s, a);
   return launch_status(name);
 }

@@ -95,7 +95,7 @@ class RobustPlan(ctypes.Structure):
         ("check", CheckPlan),
         ("a", ctypes.c_uint32 * MAX_RESOLVE),
         ("negate", ctypes.c_uint32),
-        ("reserved", ctypes.c_uint32),
+        ("max_errors", ctypes.c_uint32),
         ("div", DivSmall * (MAX_RESOLVE + 1)),
     ]
 
@@ -160,6 +160,7 @@ _SYMBOLS = {
     "dn_m521_reconstruct_robust": (i32, [pvp, ctypes.POINTER(RobustPlan), vp, vp, vp, vp, u64, vp], False),
     "dn_m521_reconstruct_records_robust": (i32, [pvp, pu64, pvp, pu64, ctypes.POINTER(RobustPlan), vp, vp, vp, vp, vp,
                                                  u64, vp], False),
+    "dn_m521_robust_plan2": (i32, [pu64, i32, i32, i32, ctypes.POINTER(RobustPlan)], False),
 }
 EXPORTS = tuple(_SYMBOLS)
 
@@ -492,15 +493,21 @@ def check_records(wires: Sequence, xs: Sequence[int], plan: CheckPlan, counts, b
                                   ctypes.byref(plan), _ptr(counts), _ptr(culprit), _ptr(bad), n, stream_ptr()))
 
 
-def robust_plan(xs: Sequence[int], threshold: int) -> RobustPlan:
+def robust_plan(xs: Sequence[int], threshold: int, errors: int = 1) -> RobustPlan:
     """`check_plan` with the all-k Lagrange integers and the division
     constants of a robust reconstruct (dn_m521_robust_plan; host only).
     Raises as `check_plan` does, and NotImplementedError for one spare share
-    and for the plan's own bounds."""
-    L = need(lib(), "dn_m521_robust_plan")
+    and for the plan's own bounds.  errors=2 asks for the two-error finish
+    (dn_m521_robust_plan2): NotImplementedError unless there are exactly four
+    spare shares and every pair's sum, product and difference is in range;
+    ValueError for any other value than 1 or 2."""
     plan = RobustPlan()
     arr = (ctypes.c_uint64 * max(1, len(xs)))(*[int(x) for x in xs])
-    check(L.dn_m521_robust_plan(arr, len(xs), threshold, ctypes.byref(plan)))
+    if errors == 1:
+        check(need(lib(), "dn_m521_robust_plan").dn_m521_robust_plan(arr, len(xs), threshold, ctypes.byref(plan)))
+    else:
+        L = need(lib(), "dn_m521_robust_plan2")
+        check(L.dn_m521_robust_plan2(arr, len(xs), threshold, int(errors), ctypes.byref(plan)))
     return plan
 
 

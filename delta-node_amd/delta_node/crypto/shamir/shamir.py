@@ -538,7 +538,7 @@ class SecretShare(object):
         return (count, marks) if culprit else count
 
     def resolve_shares_vec_robust(self, shares, xs: Sequence[int], n: int, *, out: str = "int64",
-                                  culprit: bool = False, bad=None):
+                                  culprit: bool = False, bad=None, errors: int = 1):
         """`resolve_shares_vec` over k >= threshold + 2 share vectors that
         survives ONE bad share per element: the check of `check_shares_vec`
         and the reconstruction in one launch, every row read once
@@ -564,17 +564,30 @@ class SecretShare(object):
                  elements, bad[1] += corrected ones, on the device; the call
                  does not synchronise, can be captured into a graph, and the
                  count returned is None
+        errors   1: as above.  2: with exactly four spare shares
+                 (k == threshold + 4) an element that no single share explains
+                 is also tried against every pair of shares, in the same
+                 launch.  Where exactly one pair i < j (indices into xs)
+                 explains it, the culprit byte is 16 + j (j - 1) / 2 + i
+                 (16 .. 135: apart from the single indices 0 .. 15, 0xFE and
+                 0xFF), the result is the interpolant of the k - 2 other
+                 shares and the element counts as corrected; otherwise 0xFE
+                 as above.  Consistent and single-share elements are exactly
+                 those of errors=1
         Returns (result, count) or (result, count, culprit).
         NotImplementedError for `check_shares_vec`'s limits, for one spare
         share (k == threshold + 1 detects only) and where a Lagrange integer
-        reaches 2^32 or a divisor's odd part 2^16.  There is no CPU fallback."""
+        reaches 2^32 or a divisor's odd part 2^16; with errors=2 also unless
+        k == threshold + 4, and where some x_i + x_j or x_i x_j reaches 2^32
+        or the odd part of some x_j - x_i 2^16.  ValueError for errors other
+        than 1 or 2.  There is no CPU fallback."""
         self._require_m521()
         import torch
 
         what = "resolve_shares_vec_robust"
 
         def plan_of(xs):
-            plan = _native.robust_plan(xs, self.threshold)
+            plan = _native.robust_plan(xs, self.threshold, errors)
             _args.check_out_form(what, out)
             return plan
 
@@ -715,7 +728,7 @@ class SecretShare(object):
         return (count, marks) if culprit else count
 
     def resolve_records_vec_robust(self, records, xs: Optional[Sequence[int]], n: int, *, out: str = "int64",
-                                   culprit: bool = False, bad=None, bad_records=None):
+                                   culprit: bool = False, bad=None, bad_records=None, errors: int = 1):
         """`resolve_shares_vec_robust` straight from wire records: the secret
         of every element from k >= threshold + 2 wires, past ONE damaged wire
         per element, in one launch and without the k decoded vectors
@@ -732,6 +745,10 @@ class SecretShare(object):
         out, culprit, bad  as `resolve_shares_vec_robust`, and its return:
                  (result, count) or (result, count, culprit), count the pair of
                  ints (inconsistent, corrected), or None where bad is given
+        errors   as `resolve_shares_vec_robust`: 2 survives TWO damaged wires
+                 per element where k == threshold + 4; a located pair i < j of
+                 wires has the culprit byte 16 + j (j - 1) / 2 + i and counts
+                 as corrected
         The call synchronises only where bad or bad_records is None; with both
         given (and xs given) it can be captured into a graph.
 
@@ -755,7 +772,7 @@ class SecretShare(object):
             self._check_abscissas(xs)
             if not all(_args.fits_u64(x) for x in xs):
                 raise NotImplementedError(f"{what}: abscissas must fit 64 bits")
-            return _native.robust_plan(xs, self.threshold)
+            return _native.robust_plan(xs, self.threshold, errors)
 
         flags = [(what, bad), (what + ": bad_records", bad_records)]
         recs, xs, n, dev, plan = self._checked_wires(what, records, xs, n, flags, plan_of,

@@ -702,7 +702,8 @@ typedef struct dn_m521_robust_plan {
   uint32_t a[DN_MAX_RESOLVE];   /* |A_m|, each < 2^32; A_m has the sign of w_m,
                                    times -1 when k is even                  */
   uint32_t negate;              /* 1 when k is even: the quotient is negated */
-  uint32_t reserved;
+  uint32_t max_errors;          /* 0 or 1: one bad share per element is corrected;
+                                   2 (dn_m521_robust_plan2, r == 4 only): two   */
   dn_m521_div_small_t div[DN_MAX_RESOLVE + 1]; /* [i]: |w_i| D_all; [DN_MAX_RESOLVE]: D_all */
 } dn_m521_robust_plan_t;
 
@@ -712,6 +713,25 @@ typedef struct dn_m521_robust_plan {
  * bits, an |A_m| >= 2^32 (the same one-limb bound as the syndromes' weights),
  * and a divisor |w_i| D_all or D_all whose odd part is 2^16 or more. */
 int dn_m521_robust_plan(const uint64_t* xs, int k, int threshold, dn_m521_robust_plan_t* out);
+
+/* Host.  dn_m521_robust_plan for up to `errors` bad shares per element.
+ * errors == 1 is dn_m521_robust_plan, byte for byte.  errors == 2 asks the
+ * device entry points below for the two-error finish: with r = 4 spare shares
+ * an element's shares are a Reed-Solomon word of minimum distance 5, and where
+ * no single share explains an inconsistent element the one pair i < j
+ * (indices into xs) with
+ *   S_{m+2} - (x_i + x_j) S_{m+1} + x_i x_j S_m == 0   (mod p), m = 0, 1
+ * is located, its culprit byte is 16 + j (j - 1) / 2 + i (16 .. 135) and the
+ * output is the interpolant of the k - 2 other shares,
+ *   f(0) = T / D_all - A_i U_i / (w_i D_all delta) - A_j U_j / (w_j D_all delta),
+ *   delta = x_j - x_i, U_i = x_j S_0 - S_1, U_j = S_1 - x_i S_0;
+ * it is counted as corrected.  An element no pair explains keeps 0xFE.  After
+ * dn_m521_robust_plan's checks, in their order, DN_ERR_UNSUPPORTED for: r != 4,
+ * an x_i + x_j or x_i x_j of 2^32 or more, a |delta| whose odd part is 2^16 or
+ * more (its division constants are computed by the kernel, per corrected
+ * element; nothing is tabulated).  errors other than 1 or 2 is DN_ERR_ARG,
+ * before every other check.  The mode travels in out->max_errors. */
+int dn_m521_robust_plan2(const uint64_t* xs, int k, int threshold, int errors, dn_m521_robust_plan_t* out);
 
 /*
  * Device.  One launch, every row read once.
